@@ -1,8 +1,15 @@
 """Benchmark of the MI355X retrieval hot path (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, the
+outputs of the last timed step as .npy files when --dump-outputs is given, and the result line
+(the scan's roofline rides on event pairs recorded inside the timed steps). --full adds everything
+else the line can carry: step and single-query p50 latencies, certified_frac, the sparse stage's
+rooflines (re-runs of its kernels alone), the cpu_baseline and the secondary configurations
+(configs1 / configs2 / size sweep / hybrid / pipeline / configs3_rank, each a child run).
 
 Workload (BASELINE.json metric "queries/sec + p50 latency, 1M x 1024-d chunks, top-5"):
   a 1M x 1024 fp16 chunk store (synthetic unit vectors) sharded by chunk
@@ -241,6 +248,21 @@ def read_traffic(key: str, kernel: str) -> tuple[float | None, str | None]:
         return None, None
 
 
+def dump_outputs(out_dir: Path, top) -> None:
+    """--dump-outputs: the TopK the last timed step returned, one DIR/<name>.npy per field.
+    scores stay float32; ids, rank, count and flags are written as float64 (exact for chunk
+    ordinals and flag bits). The inputs are seeded, so two builds run with the same arguments can
+    be compared file by file."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    fields = {"scores": (top.scores, np.float32), "ids": (top.ids, np.float64),
+              "rank": (top.rank, np.float64), "count": (top.count, np.float64),
+              "flags": (top.flags, np.float64)}
+    torch.cuda.synchronize()
+    for name, (t, dtype) in fields.items():
+        if t is not None:
+            np.save(out_dir / f"{name}.npy", t.detach().cpu().numpy().astype(dtype))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -250,6 +272,13 @@ def main() -> None:
     ap.add_argument("--dim", type=int, default=1024)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--top-k", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: p50 latencies, certified_frac, the sparse stage's "
+                         "rooflines, the cpu_baseline and the secondary configurations (child "
+                         "runs); --no-cpu-baseline / --no-extras / --latency-iters trim those")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (scores, ids, rank, count, "
+                         "flags of its TopK) as DIR/<name>.npy, float32 / float64")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--eager-hybrid", action="store_true",
                     help="hybrid workloads: launch each step's kernels from Python instead of "
@@ -454,8 +483,11 @@ def main() -> None:
     barrier()
     elapsed = time.perf_counter() - t0
     rr_timing["on"] = False
+    if args.dump_outputs and rank == 0 and last is not None:
+        dump_outputs(Path(args.dump_outputs), last)
+    full = args.full
     scan_timing_note = None
-    if wl != "dense" and hgraph is not None:
+    if full and wl != "dense" and hgraph is not None:
         # The timed steps replayed the step's HIP graph, whose launches record no host-side HIP
         # events: the scans' launch times come from eager launches of the same kernels over the
         # same batches right after the timed region (the rerank, timed above, is not rerun).
@@ -471,7 +503,7 @@ def main() -> None:
         scan_timing_note = (f"scan launch times from {n_eager} eager hybrid steps of the same "
                             "batches after the timed region (the timed steps replay a HIP graph)")
     sparse_timing = {}
-    if wl != "dense" and sindex is not None and world == 1:
+    if full and wl != "dense" and sindex is not None and world == 1:
         # the sparse stage inside the step shares the GPU with the dense scan (two streams); its
         # own duration: the same calls alone on the stream, right after
         for slot, key in ((_armi.TIMING_SPARSE_SCAN, "scan_in_step"),
@@ -498,7 +530,7 @@ def main() -> None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     certified = None
-    if wl == "dense" and last is not None and last.flags is not None:
+    if full and wl == "dense" and last is not None and last.flags is not None:
         # over every query batch of the run (first-pass certificate; the rest took the second pass)
         if sharded is None:
             fls = []
@@ -513,13 +545,14 @@ def main() -> None:
 
     # p50 latency of one step (batch of 64 per GPU) and of a single query
     lat, lat1 = [], []
-    for i in range(args.latency_iters):
+    latency_iters = args.latency_iters if full else 0
+    for i in range(latency_iters):
         barrier()
         t1 = time.perf_counter()
         step(i)
         barrier()
         lat.append(time.perf_counter() - t1)
-    for i in range(args.latency_iters):
+    for i in range(latency_iters):
         barrier()
         t1 = time.perf_counter()
         step(i, queries[i % n_q_batches][:1])
@@ -593,8 +626,8 @@ def main() -> None:
             "parallelism": f"corpus-shard{world}" + ("" if backend == "nccl" or world == 1
                                                       else f" ({backend} rehearsal, shared GPUs)"),
         },
-        "p50_ms": statistics.median(lat) * 1e3,
-        "p50_single_query_ms": statistics.median(lat1) * 1e3,
+        "p50_ms": statistics.median(lat) * 1e3 if lat else None,
+        "p50_single_query_ms": statistics.median(lat1) * 1e3 if lat1 else None,
         "certified_frac": certified,
         "roofline": ({
             "bound": "hbm",
@@ -627,6 +660,10 @@ def main() -> None:
             "launches_timed": launches.value,
         }),
     }
+    if not launches.value:
+        # no timed launch of the scan (fewer steps than the timing period, or graph replays in a
+        # plain hybrid run): no roofline rather than one of NaNs
+        result["roofline"] = None
     if reranker is not None and rr_timing["events"]:
         # configs[2]: the cross-encoder is the dominant (MFMA-bound) stage; the scan roofline
         # moves to roofline_scan
@@ -648,7 +685,7 @@ def main() -> None:
             "forwards_timed": len(rr_timing["events"]),
         }
         result["rerank_share_of_step"] = (rr_ms * 1e-3) / elapsed
-    if sindex is not None and world == 1:
+    if full and sindex is not None and world == 1:
         # sparse roofline of the dominant sparse kernel. With the MFMA filter (every query of a
         # pass answered by it: ARMI_FLAG_FILTERED) that is sparse_filter_scan_kernel, whose
         # algorithmic bytes per 64-query pass are the u8 levels of the pass's dense-column terms
@@ -704,7 +741,7 @@ def main() -> None:
     if scan_timing_note:
         result["scan_timing"] = scan_timing_note
     result["cpu_baseline"] = None
-    if world == 1 and not args.no_cpu_baseline:
+    if full and world == 1 and not args.no_cpu_baseline:
         ref = CpuReference(rows, csr)
         qn = queries.reshape(-1, dim).float().cpu().numpy()
         q_csr = None
@@ -727,7 +764,7 @@ def main() -> None:
         result["cpu_baseline"] = cpu_baseline(wl, ref, qn, q_csr, k, search_k, pairs,
                                               budget_s=args.cpu_budget)
         del ref
-    if wl == "dense" and world == 1 and not args.no_extras and args.corpus == "random":
+    if full and wl == "dense" and world == 1 and not args.no_extras and args.corpus == "random":
         result.update(secondary_configs(args))
     print(json.dumps(result), flush=True)
     if distributed:
@@ -770,7 +807,7 @@ def secondary_configs(args) -> dict:
     }
     out = {}
     for key, extra in runs.items():
-        cmd = [sys.executable, str(ROOT / "bench.py"), "--no-extras", *extra]
+        cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--no-extras", *extra]
         if key not in ("configs1", "configs2", "hybrid"):
             cmd.append("--no-cpu-baseline")
         try:

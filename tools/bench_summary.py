@@ -1,4 +1,4 @@
-"""One-screen summary of a bench.py JSON line (the default run's headline and child objects).
+"""One-screen summary of a bench.py JSON line (a --full run's headline and child objects).
 Usage: python tools/bench_summary.py BENCH_JSON"""
 import json
 import sys

@@ -1,12 +1,14 @@
 #!/bin/bash
-# The driver's default bench line (dense headline + configs1 / configs2 / 10k / 10M children), timed.
+# The full bench line (dense headline + configs1 / configs2 / 10k / 10M children), timed.
+# Output goes to $OUT (default bench_out/) under the repository root.
 TAG=${1:-r03w}
-R="$GRAFT_REPO_ROOT"; cd "$R" || exit 1; mkdir -p gpurun_out
+R="$(cd "$(dirname "$0")/.." && pwd)"; cd "$R" || exit 1
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"
 T0=$(date +%s)
-timeout -k 10 900 python bench.py > gpurun_out/${TAG}_bench_dense.log 2>&1; rc=$?
+timeout -k 10 900 python bench.py --full > "$OUT/${TAG}_bench_dense.log" 2>&1; rc=$?
 echo "rc=$rc secs=$(( $(date +%s) - T0 ))"
 [ $rc -eq 0 ] || exit $rc
-tail -1 gpurun_out/${TAG}_bench_dense.log | python -c "
+tail -1 "$OUT/${TAG}_bench_dense.log" | python -c "
 import json, sys
 d = json.loads(sys.stdin.read())
 print('dense', round(d['value']), round(d['ms_per_step'], 4), round(d['roofline']['frac'], 3))

@@ -7,7 +7,7 @@ TAG=$1; FIELD=$2; shift 2
 R="$GRAFT_REPO_ROOT"
 cd /tmp && export TMPDIR=/tmp
 mkdir -p "$R/gpurun_out/traffic"
-B="$R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras --latency-iters 2 $*"
+B="$R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-extras --latency-iters 2 $*"
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout -k 10 240 rocprofv3 --pmc $c --output-format csv -d "$R/gpurun_out/${TAG}_$c" -o run -- python3 $B > "$R/gpurun_out/${TAG}_$c.log" 2>&1 || exit $?
 done
