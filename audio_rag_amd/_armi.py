@@ -24,7 +24,7 @@ ARMI_FLAG_FALLBACK = 2
 ARMI_FLAG_FILTERED = 4
 TIMING_DENSE_SCAN, TIMING_SPARSE_SCAN, TIMING_ENCODER_GEMM, TIMING_SPARSE_STAGE = 0, 1, 2, 3
 SCAN_FP16, SCAN_INT8_FILTER, SCAN_TILED_FP16, SCAN_TILED_INT8 = 0, 1, 2, 3  # armi_dense_scan_form
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 c_void_p = ctypes.c_void_p
 c_int = ctypes.c_int
@@ -39,6 +39,14 @@ SIGNATURES: dict[str, tuple] = {
     "armi_abi_version": (c_int, []),
     "armi_source_digest": (ctypes.c_char_p, []),
     "armi_index_create": (c_int, [c_int, c_void_p, c_int64, c_int, c_int64, ctypes.POINTER(c_void_p), c_void_p]),
+    "armi_index_create_tail": (c_int, [c_int, c_int, c_int64, c_int64, ctypes.POINTER(c_void_p), c_void_p]),
+    "armi_index_append": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "armi_index_capacity": (c_int64, [c_void_p]),
+    "armi_dense_tail_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "armi_dense_tail_list_cap": (c_int, []),
+    "armi_dense_tail_topk": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_size_t, c_void_p]),
     "armi_dense_scan_form": (c_int, [c_void_p, c_int, c_int]),
     "armi_dense_scan_nontemporal": (c_int, [c_void_p, c_int, c_int]),
     "armi_index_destroy": (c_int, [c_void_p]),

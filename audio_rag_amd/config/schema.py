@@ -61,6 +61,12 @@ class RetrievalConfig(BaseModel):
     # (torchrun), torch.distributed initialised before the retriever; searches are collective
     # calls (MI355XRetriever._search_sharded)
     num_gpus: int = Field(default=1, ge=1)
+    # live ingest: > 0 keeps points added after a collection's first build in a small growable fp16
+    # segment (the "tail", nominally this many rows) that is searched together with the built
+    # indexes and folded into them when it fills, so an add costs time proportional to the new
+    # points. 0: every add rebuilds the indexes on the next search. Ignored (rebuild) with
+    # num_gpus > 1 and for collections built from device indexes
+    live_tail_rows: int = Field(default=0, ge=0)
 
 
 class RerankingConfig(BaseModel):

@@ -32,6 +32,12 @@ struct armi_index {
   int64_t perm_mul = 1;
   int64_t perm_inv = 1;
   int32_t* tile_ord = nullptr;   // [n_tiles] ordinal of image tile tau's row 0 = tau * perm_inv mod T
+  // Growable fp16 segment (armi_index_create_tail): the index owns its row buffer and the norm
+  // arrays are sized for `capacity` rows (whole tiles; rows past n_rows are padding). It has no
+  // int8 image (rows8 == a32 == e32 == tile_ord == nullptr): every search takes its fp16 form and
+  // the exact second pass. capacity == 0: an immutable index over caller-owned rows.
+  uint16_t* owned_rows = nullptr;  // [capacity][dim], == rows
+  int64_t capacity = 0;
 };
 
 namespace armi {

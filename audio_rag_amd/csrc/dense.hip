@@ -2564,7 +2564,9 @@ Workspace carve(void* base, const armi_index* idx, int nq, int k, bool fast) {
   }
   w.inv_q = cv.take<double>(nq);
   w.qnorm = cv.take<double>(nq);
-  if (!fast) {
+  // (an index without the int8 image - a growable tail - answers its uncertified queries by the
+  // exhaustive exact pass instead of the int8 collect pass)
+  if (!fast || idx->rows8 == nullptr) {
     const ExactPlan ep = plan_exact(idx, k);
     w.ex_key = cv.take<double>((size_t)nq * ep.n_blocks * ep.cap);
     w.ex_ord = cv.take<int64_t>((size_t)nq * ep.n_blocks * ep.cap);
@@ -2615,7 +2617,7 @@ int dense_topk_impl(const armi_index* idx, const uint16_t* queries, int nq, int 
   const int64_t T = std::max<int64_t>(idx->n_tiles, 1);
   // the int8 passes (first pass and collect pass) read the filter in image order
   const uint64_t* mask_i8 = nullptr;
-  if (row_mask) {
+  if (row_mask && idx->rows8 != nullptr) {
     scan_prep_kernel<<<dim3((unsigned)std::max<int64_t>(1, (T * 32 + 255) / 256)), dim3(256), 0,
                        stream>>>(row_mask, idx->n_rows, T, idx->tile_ord, w.mask_img);
     ARMI_LAUNCHED("scan_prep_kernel");
@@ -2697,6 +2699,9 @@ int dense_second_pass(const armi_index* idx, const uint16_t* queries, int nq, in
                       const uint64_t* row_mask, const uint64_t* mask_i8, float* out_scores,
                       int64_t* out_ids, double* out_rank, int32_t* out_count, uint32_t* out_flags,
                       const Workspace& w, hipStream_t stream) {
+  if (idx->rows8 == nullptr)  // no int8 image to collect from: the exact scan, flagged queries only
+    return launch_exact<DIM>(idx, queries, nq, k, row_mask, out_scores, out_ids, out_rank, out_count,
+                             out_flags, 1, w, stream);
   {
     const ScanPlan cp = plan_scan(idx, k, 1);  // one block's ranges; blocks of one range share an XCD
     const int n_qb = (nq + kQB - 1) / kQB;
@@ -2720,6 +2725,351 @@ int dense_second_pass(const armi_index* idx, const uint16_t* queries, int nq, in
       out_rank, out_count, out_flags);
   ARMI_LAUNCHED("dense_collect_merge_kernel");
   return ARMI_OK;
+}
+
+
+// ------------------------------------------------------------------------------ live tail pass
+// armi_dense_tail_topk: the global top-k of a finished list over the main segment and a small
+// growable fp16 segment (armi_index_create_tail), without a top-k of the tail alone. The main
+// list's k-th exact key is a lower bound of the global k-th, so a tail row can only matter when
+// its exact key reaches it, i.e. (|approx - exact| <= delta, the scan's certificate) when its
+// approximate key reaches thr = kth - delta rounded down (-inf when the main list holds fewer
+// than k). Two launches:
+//   dense_tail_scan    dense_scan_kernel's tile loop (same MFMA operands, same inv_norm32 scaling)
+//                      over 8 tiles per workgroup, with an epilogue that keeps no lane lists: a
+//                      (row, query) pair at or above the query's thr is appended to the
+//                      workgroup's own list of that query (256 slots = its rows: it cannot
+//                      overflow, and its count is written, not accumulated: nothing to zero)
+//   dense_tail_finish  one workgroup per query: gathers the workgroup lists, computes the exact
+//                      keys of the survivors (of every tail row when more than kTailCap
+//                      survived) and merges them with the main list by (key desc, ordinal asc)
+constexpr int kTailCap = kSelCap;        // survivors rescored per query; more: the exhaustive pass
+constexpr int kTailTilesPerWg = kWaves;  // one tile per wave
+constexpr int kTailWgRows = kTailTilesPerWg * TILE_ROWS;
+
+template <int DIM>
+constexpr int tail_scan_lds_bytes() { return scan_lds_bytes<DIM>() + kQB * 8 + kWaves * kQB * 8; }
+
+template <int DIM>
+__global__ __launch_bounds__(kThreads) void dense_tail_scan_kernel(
+    const uint16_t* __restrict__ rows, const float* __restrict__ inv_norm32,
+    const uint64_t* __restrict__ row_mask, int64_t n_rows, int64_t n_tiles,
+    const uint16_t* __restrict__ queries_all, int nq_all, int k,
+    const double* __restrict__ main_rank, const int32_t* __restrict__ main_count,
+    int32_t* __restrict__ wg_cnt, int32_t* __restrict__ wg_list) {
+  constexpr int KSTEPS = DIM / 16;
+  constexpr int GROUPS = DIM / 64;
+  static_assert(GROUPS % kDepth == 0, "prefetch ring must divide the tile");
+  const int q0 = blockIdx.y * kQB;
+  const int nq = min(kQB, nq_all - q0);
+  const int n_wg = gridDim.x;
+  const uint16_t* __restrict__ queries = queries_all + (size_t)q0 * DIM;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  u32x4* qimg = reinterpret_cast<u32x4*>(smem);  // [KSTEPS][2][kQB] 16-byte fragments
+  float* s_thr = reinterpret_cast<float*>(smem + scan_lds_bytes<DIM>());       // [kQB]
+  int* s_cnt = reinterpret_cast<int*>(smem + scan_lds_bytes<DIM>() + kQB * 4);  // [kQB]
+  int64_t* s_n2 = reinterpret_cast<int64_t*>(smem + scan_lds_bytes<DIM>() + kQB * 8);  // [kWaves][kQB]
+
+  const int wave = armi::wave_id();
+  const int lane = threadIdx.x & 63;
+  const int r = lane & 31;
+  const int h = lane >> 5;
+  const int64_t t_begin = (int64_t)blockIdx.x * kTailTilesPerWg;
+  const int64_t t_end = min(t_begin + (int64_t)kTailTilesPerWg, n_tiles);
+  int64_t t = t_begin + wave;
+  auto row_ptr = [&](int64_t tile) -> const u32x4* {
+    int64_t rr = tile * TILE_ROWS + r;
+    rr = rr < n_rows ? rr : n_rows - 1;
+    return reinterpret_cast<const u32x4*>(rows + rr * DIM) + 4 * h;
+  };
+  const u32x4* cur = row_ptr(t < t_end ? t : t_begin);
+  u32x4 buf[kDepth][4];
+  if (t < t_end) {
+#pragma unroll
+    for (int g = 0; g < kDepth; ++g)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) buf[g][i] = stream_load(cur + 8 * g + i);
+  }
+  // the query fragment image of dense_scan_kernel (K-step s, lane half h: chunk 8*(s/4)+4*h+s%4).
+  // A thread stages chunks of one query (kThreads is a multiple of kQB: q = lane), so the exact
+  // query norms fall out of the same loads: the sum of squares of the thread's chunks, the eight
+  // waves' partials of a query added through LDS (int64: any order gives the same bits).
+  static_assert(kThreads % kQB == 0 && kQB == 64, "one query per staging thread");
+  int64_t n2 = 0;
+  for (int e = threadIdx.x; e < KSTEPS * 2 * kQB; e += kThreads) {
+    const int q = e & (kQB - 1);
+    const int sh = e >> 6;
+    const int hh = sh & 1;
+    const int s = sh >> 1;
+    const int c = 8 * (s >> 2) + 4 * hh + (s & 3);
+    u32x4 v = {0u, 0u, 0u, 0u};
+    if (q < nq) v = *reinterpret_cast<const u32x4*>(queries + (size_t)q * DIM + 8 * c);
+    qimg[e] = v;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int64_t lo = armi::fp16_to_fixed24(v[i] & 0xffffu), hi = armi::fp16_to_fixed24(v[i] >> 16);
+      n2 += lo * lo + hi * hi;
+    }
+  }
+  s_n2[wave * kQB + lane] = n2;
+  __syncthreads();
+  // thresholds of the block's queries (+inf: no such query)
+  if (threadIdx.x < kQB) {
+    const int ql = threadIdx.x;
+    float thr = __builtin_inff();
+    if (ql < nq) {
+      int64_t n2q = 0;
+#pragma unroll
+      for (int w = 0; w < kWaves; ++w) n2q += s_n2[w * kQB + ql];
+      const double qnorm_real = sqrt((double)n2q) * (1.0 / 16777216.0);
+      const double delta = kDeltaSafety * (double)DIM * (1.0 / 16777216.0) * qnorm_real;
+      thr = kNegInf;
+      if (main_count[q0 + ql] >= k)
+        thr = f32_round_down(main_rank[(size_t)(q0 + ql) * k + k - 1] * (1.0 / 16777216.0) - delta);
+    }
+    s_thr[ql] = thr;
+    s_cnt[ql] = 0;
+  }
+  __syncthreads();
+  // this lane's two queries (accumulator columns r and 32 + r)
+  const float thr0 = s_thr[r], thr1 = s_thr[32 + r];
+  int32_t* list0 = wg_list + ((size_t)(q0 + r) * n_wg + blockIdx.x) * kTailWgRows;
+  int32_t* list1 = wg_list + ((size_t)(q0 + 32 + r) * n_wg + blockIdx.x) * kTailWgRows;
+
+  for (; t < t_end; t += kWaves) {
+    const int64_t tn = (t + kWaves < t_end) ? t + kWaves : t_begin;
+    const u32x4* nxt = row_ptr(tn);
+    int qoff = h * kQB + r;
+    asm volatile("" : "+v"(qoff));  // keeps the fragment reads inside the tile loop
+    const u32x4* qv = qimg + qoff;
+    f32x16 acc0 = {}, acc1 = {};
+    float4 iv4[4];
+#pragma unroll
+    for (int g = 0; g < GROUPS; ++g) {
+      u32x4 a[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) a[i] = buf[g % kDepth][i];
+      if (g == GROUPS - kDepth) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          iv4[q] = *reinterpret_cast<const float4*>(inv_norm32 + t * TILE_ROWS + 8 * q + 4 * h);
+      }
+      if (g + kDepth < GROUPS) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) buf[g % kDepth][i] = stream_load(cur + 8 * (g + kDepth) + i);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          buf[g % kDepth][i] = stream_load(nxt + 8 * (g + kDepth - GROUPS) + i);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int s = 4 * g + i;
+        const u32x4 b0 = qv[s * 2 * kQB];
+        const u32x4 b1 = qv[s * 2 * kQB + 32];
+        acc0 = mfma16(a[i], b0, acc0);
+        acc1 = mfma16(a[i], b1, acc1);
+      }
+    }
+    cur = nxt;
+
+    // Epilogue: lane holds rows (j&3) + 8*(j>>2) + 4*h of the tile, queries r and 32 + r. Padding
+    // and invalid rows carry a NaN inverse norm, filtered rows get one here: NaN >= thr is false.
+    // (A (row, query) pair is seen once, so a workgroup's list takes at most its kTailWgRows rows.)
+    const int64_t row0 = t * TILE_ROWS;
+    float inv[16];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const float4 v = iv4[q];
+      inv[4 * q + 0] = v.x; inv[4 * q + 1] = v.y; inv[4 * q + 2] = v.z; inv[4 * q + 3] = v.w;
+    }
+    if (row_mask) {
+      const uint32_t mbits = (uint32_t)(row_mask[row0 >> 6] >> (row0 & 63));
+#pragma unroll
+      for (int j = 0; j < 16; ++j)
+        if (!((mbits >> ((j & 3) + 8 * (j >> 2) + 4 * h)) & 1u)) inv[j] = __builtin_nanf("");
+    }
+    const int32_t rbase = (int32_t)row0 + 4 * h;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const int32_t row = rbase + (j & 3) + 8 * (j >> 2);
+      if (acc0[j] * inv[j] >= thr0) {
+        const int slot = atomicAdd(s_cnt + r, 1);
+        if (slot < kTailWgRows) list0[slot] = row;
+      }
+      if (acc1[j] * inv[j] >= thr1) {
+        const int slot = atomicAdd(s_cnt + 32 + r, 1);
+        if (slot < kTailWgRows) list1[slot] = row;
+      }
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < nq)
+    wg_cnt[(size_t)(q0 + threadIdx.x) * n_wg + blockIdx.x] = min(s_cnt[threadIdx.x], kTailWgRows);
+}
+
+// LDS of dense_tail_finish_kernel: collect_top_rows' sort arrays, the gathered survivor rows, one
+// chunk of workgroup counts / offsets, the total.
+constexpr size_t kTailSortLds = 2 * kTailCap * 16;  // (key, ordinal) x (survivors + main list)
+constexpr size_t kTailFinishLds = kTailSortLds + kTailCap * 4 + 64 * 8 + 16;
+
+template <int DIM>
+__global__ __launch_bounds__(kDenseMergeThreads) void dense_tail_finish_kernel(
+    const int32_t* __restrict__ wg_cnt, const int32_t* __restrict__ wg_list, int n_wg,
+    const uint16_t* __restrict__ rows, const double* __restrict__ inv_norm,
+    const int64_t* __restrict__ norm2, const uint64_t* __restrict__ row_mask, int64_t n_rows,
+    const uint16_t* __restrict__ queries, int k, int64_t ordinal_base,
+    const int64_t* __restrict__ main_ids, const double* __restrict__ main_rank,
+    const int32_t* __restrict__ main_count, float* __restrict__ out_scores,
+    int64_t* __restrict__ out_ids, double* __restrict__ out_rank, int32_t* __restrict__ out_count,
+    uint32_t* __restrict__ out_flags) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  double* key = reinterpret_cast<double*>(smem);                       // [2 * kTailCap]
+  int64_t* ord = reinterpret_cast<int64_t*>(smem + 2 * kTailCap * 8);   // [2 * kTailCap]
+  int32_t* s_list = reinterpret_cast<int32_t*>(smem + kTailSortLds);   // [kTailCap]
+  int* s_c = reinterpret_cast<int*>(smem + kTailSortLds + kTailCap * 4);  // [64] counts of a chunk
+  int* s_o = s_c + 64;                                                  // [64] their offsets
+  int* s_total = s_o + 64;
+  const int qg = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = armi::wave_id();
+  int32_t qf[DIM / 64];
+  load_fixed<DIM>(queries + (size_t)qg * DIM, lane, qf);
+  int64_t n2q = 0;
+#pragma unroll
+  for (int i = 0; i < DIM / 64; ++i) n2q += (int64_t)qf[i] * (int64_t)qf[i];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) n2q += armi::xor_stride(n2q, off);
+  const double iq = n2q > 0 ? 1.0 / sqrt((double)n2q) : 0.0;
+  // gather the workgroup lists (64 workgroups at a time) into s_list, in workgroup order
+  int base = 0;  // survivors before this chunk (uniform)
+  for (int w0 = 0; w0 < n_wg; w0 += 64) {
+    if (wave == 0) {
+      const int w = w0 + lane;
+      const int c = w < n_wg ? wg_cnt[(size_t)qg * n_wg + w] : 0;
+      int incl = c;
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const int v = __shfl_up(incl, off);
+        if (lane >= off) incl += v;
+      }
+      s_c[lane] = c;
+      s_o[lane] = base + incl - c;
+      if (lane == 63) *s_total = base + incl;
+    }
+    __syncthreads();
+    for (int e = tid; e < 64 * kTailWgRows; e += kDenseMergeThreads) {
+      const int wl = e / kTailWgRows, j = e % kTailWgRows;
+      const int at = s_o[wl] + j;
+      if (j < s_c[wl] && at < kTailCap)
+        s_list[at] = wg_list[((size_t)qg * n_wg + w0 + wl) * kTailWgRows + j];
+    }
+    base = *s_total;
+    __syncthreads();
+  }
+  const int cnt = base;
+  const bool overflow = cnt > kTailCap;  // workgroup-uniform
+  // the tail's candidates in [0, p): the survivors' exact keys (eight rows per wave and round), or
+  // after an overflow the best of every row
+  int p;
+  if (!overflow) {
+    p = max(8, armi::pow2_at_least(cnt > k ? cnt : k));
+    for (int e = tid; e < p; e += kDenseMergeThreads) {
+      key[e] = kNegInfD;
+      ord[e] = kNoOrd;
+    }
+    __syncthreads();
+    for (int b = 8 * wave; b < cnt; b += 8 * (kDenseMergeThreads / 64)) {
+      int32_t rr[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) rr[j] = b + j < cnt ? s_list[b + j] : -1;
+      double kk;
+      int32_t myrow;
+      exact_keys8<DIM>(qf, rows, inv_norm, rr, lane, kk, myrow);
+      if ((lane & 7) == 0 && myrow >= 0) {
+        const int e = b + ((lane >> 3) & 7);
+        key[e] = kk;
+        ord[e] = ordinal_base + myrow;
+      }
+    }
+  } else {
+    collect_top_rows<DIM>(nullptr, 0, n_rows, k, qf, rows, inv_norm, norm2, row_mask, ordinal_base,
+                          key, ord);
+    p = n_rows <= kColChunk ? armi::pow2_at_least((int)n_rows > k ? (int)n_rows : k) : kColChunk;
+  }
+  // the main list behind them (p >= k), then one sort of both
+  const int main_n = min(max(main_count[qg], 0), k);
+  for (int e = p + tid; e < 2 * p; e += kDenseMergeThreads) {
+    const int c = e - p;
+    const bool v = c < main_n && main_ids[(size_t)qg * k + c] >= 0;
+    key[e] = v ? main_rank[(size_t)qg * k + c] : kNegInfD;
+    ord[e] = v ? main_ids[(size_t)qg * k + c] : kNoOrd;
+  }
+  armi::lds_sort_rank_desc(key, ord, 2 * p);
+  if (wave != 0) return;
+  int n_valid = 0;
+  for (int c = lane; c < k; c += 64) n_valid += ord[c] != kNoOrd;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) n_valid += armi::xor_stride(n_valid, off);
+  for (int c = lane; c < k; c += 64) {
+    const size_t o = (size_t)qg * k + c;
+    const bool v = ord[c] != kNoOrd;
+    out_scores[o] = v ? (float)(key[c] * iq) : kNegInf;
+    out_ids[o] = v ? ord[c] : -1;
+    if (out_rank) out_rank[o] = v ? key[c] : kNegInfD;
+  }
+  if (lane == 0) {
+    out_count[qg] = n_valid;
+    out_flags[qg] = overflow ? ARMI_FLAG_FALLBACK : ARMI_FLAG_CERTIFIED;
+  }
+}
+
+// ARMI_TAIL_PASS=general forces armi_dense_tail_topk's general path (armi_dense_topk over the tail,
+// then armi_topk_merge_shards); read per call: tests and A/B runs switch in-process.
+bool tail_general_path() {
+  const char* e = getenv("ARMI_TAIL_PASS");
+  return e && e[0] == 'g';
+}
+
+// workgroups of the tail scan: sized by the capacity, so an append does not grow the workspace
+int tail_wgs(const armi_index* tail, bool capacity) {
+  const int64_t rows = capacity ? std::max(tail->capacity, tail->n_tiles * TILE_ROWS)
+                                : tail->n_tiles * TILE_ROWS;
+  return (int)std::max<int64_t>(1, (rows + kTailWgRows - 1) / kTailWgRows);
+}
+
+struct TailWorkspace {
+  int32_t* wg_cnt;   // [nq][n_wg]
+  int32_t* wg_list;  // [nq][n_wg][kTailWgRows]
+  // general path: [2][nq][k] lists (0 = the main list's copy, 1 = the tail's) and the tail call's
+  // own workspace
+  double* g_rank;
+  int64_t* g_ids;
+  float* g_scores;
+  int32_t* g_count;
+  double* g_out_rank;  // [nq][k] when the caller passes no out_rank
+  char* g_ws;
+  size_t g_ws_bytes;
+  size_t bytes;
+};
+
+TailWorkspace carve_tail(void* base, const armi_index* tail, int nq, int k) {
+  armi::Carver cv(base);
+  TailWorkspace w{};
+  const size_t wgs = (size_t)tail_wgs(tail, true);
+  w.wg_cnt = cv.take<int32_t>((size_t)nq * wgs);
+  w.wg_list = cv.take<int32_t>((size_t)nq * wgs * kTailWgRows);
+  w.g_rank = cv.take<double>((size_t)2 * nq * k);
+  w.g_ids = cv.take<int64_t>((size_t)2 * nq * k);
+  w.g_scores = cv.take<float>((size_t)2 * nq * k);
+  w.g_count = cv.take<int32_t>((size_t)2 * nq);
+  w.g_out_rank = cv.take<double>((size_t)nq * k);
+  w.g_ws_bytes = armi_dense_workspace_bytes(tail, nq, k);
+  w.g_ws = cv.take<char>(w.g_ws_bytes);
+  w.bytes = cv.off + 256;
+  return w;
 }
 
 template <typename F>
@@ -2828,6 +3178,66 @@ int armi_dense_exact_topk(const armi_index* idx, const uint16_t* queries, int n_
     ARMI_LAUNCHED("query_norms_kernel");
     return launch_exact<DIM>(idx, queries, n_queries, k, row_mask, out_scores, out_ids, rank,
                              out_count, flags, 0, w, stream);
+  });
+}
+
+int armi_dense_tail_list_cap(void) { return kTailCap; }
+
+size_t armi_dense_tail_workspace_bytes(const armi_index* tail, int n_queries, int k) {
+  if (!tail || n_queries <= 0 || k <= 0) return 0;
+  k = std::min(k, kMaxK);
+  return armi::align_up(carve_tail(nullptr, tail, n_queries, k).bytes, 256);
+}
+
+int armi_dense_tail_topk(const armi_index* tail, const uint16_t* queries, int n_queries, int k,
+                         const uint64_t* tail_row_mask, const float* main_scores,
+                         const int64_t* main_ids, const double* main_rank,
+                         const int32_t* main_count, float* out_scores, int64_t* out_ids,
+                         double* out_rank, int32_t* out_count, uint32_t* out_flags,
+                         void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  ARMI_REQUIRE(tail != nullptr, "armi_dense_tail_topk: index is null");
+  ARMI_REQUIRE(n_queries >= 0, "armi_dense_tail_topk: n_queries < 0");
+  ARMI_REQUIRE(k >= 1 && k <= kMaxK, "armi_dense_tail_topk: k must be in [1, 240]");
+  if (n_queries == 0) return ARMI_OK;
+  ARMI_REQUIRE(queries && main_scores && main_ids && main_rank && main_count && out_scores &&
+                   out_ids && out_count && out_flags && workspace,
+               "armi_dense_tail_topk: null pointer argument");
+  ARMI_REQUIRE(workspace_bytes >= armi_dense_tail_workspace_bytes(tail, n_queries, k),
+               "armi_dense_tail_topk: workspace too small");
+  ARMI_HIP(hipSetDevice(tail->device));
+  const TailWorkspace w = carve_tail(workspace, tail, n_queries, k);
+  const int nq = n_queries;
+  if (tail_general_path()) {
+    const size_t nk = (size_t)nq * k;
+    ARMI_HIP(hipMemcpyAsync(w.g_rank, main_rank, nk * 8, hipMemcpyDeviceToDevice, stream));
+    ARMI_HIP(hipMemcpyAsync(w.g_ids, main_ids, nk * 8, hipMemcpyDeviceToDevice, stream));
+    ARMI_HIP(hipMemcpyAsync(w.g_scores, main_scores, nk * 4, hipMemcpyDeviceToDevice, stream));
+    ARMI_HIP(hipMemcpyAsync(w.g_count, main_count, (size_t)nq * 4, hipMemcpyDeviceToDevice, stream));
+    if (int rc = armi_dense_topk(tail, queries, nq, k, tail_row_mask, w.g_scores + nk, w.g_ids + nk,
+                                 w.g_rank + nk, w.g_count + nq, out_flags, w.g_ws, w.g_ws_bytes,
+                                 stream))
+      return rc;
+    return armi_topk_merge_shards(w.g_rank, w.g_scores, w.g_ids, w.g_count, 2, nq, k, k,
+                                  out_rank ? out_rank : w.g_out_rank,
+                                  out_scores, out_ids, out_count, stream);
+  }
+  return dispatch_dim(tail->dim, [&](auto D) {
+    constexpr int DIM = decltype(D)::value;
+    const int n_wg = tail_wgs(tail, false);
+    if (tail->n_rows > 0) {
+      if (int rc = allow_lds(dense_tail_scan_kernel<DIM>, tail_scan_lds_bytes<DIM>())) return rc;
+      dense_tail_scan_kernel<DIM><<<dim3(n_wg, (nq + kQB - 1) / kQB), dim3(kThreads),
+                                    tail_scan_lds_bytes<DIM>(), stream>>>(
+          tail->rows, tail->inv_norm32, tail_row_mask, tail->n_rows, tail->n_tiles, queries, nq, k,
+          main_rank, main_count, w.wg_cnt, w.wg_list);
+      ARMI_LAUNCHED("dense_tail_scan_kernel");
+    }
+    dense_tail_finish_kernel<DIM><<<dim3(nq), dim3(kDenseMergeThreads), kTailFinishLds, stream>>>(
+        w.wg_cnt, w.wg_list, tail->n_rows > 0 ? n_wg : 0, tail->rows, tail->inv_norm, tail->norm2,
+        tail_row_mask, tail->n_rows, queries, k, tail->ordinal_base, main_ids, main_rank,
+        main_count, out_scores, out_ids, out_rank, out_count, out_flags);
+    ARMI_LAUNCHED("dense_tail_finish_kernel");
+    return ARMI_OK;
   });
 }
 

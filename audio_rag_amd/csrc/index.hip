@@ -14,15 +14,17 @@
 
 namespace {
 
-// One wave per row: exact int64 sum of squares of the fixed-point (x * 2^24) image.
+// One wave per row, rows [row0, n_padded): exact int64 sum of squares of the fixed-point
+// (x * 2^24) image (row0 > 0: the rows an append added to a growable index).
 __global__ __launch_bounds__(256) void row_norms_kernel(const uint16_t* __restrict__ rows,
-                                                        int64_t n_rows, int64_t n_padded,
+                                                        int64_t row0, int64_t n_rows,
+                                                        int64_t n_padded,
                                                         int dim, int64_t* __restrict__ norm2,
                                                         double* __restrict__ inv_norm,
                                                         float* __restrict__ inv_norm32,
                                                         unsigned long long* __restrict__ invalid) {
   const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + armi::wave_id();
+  const int64_t row = row0 + (int64_t)blockIdx.x * 4 + armi::wave_id();
   if (row >= n_padded) return;
   if (row >= n_rows) {  // tile padding: never a result
     if (lane == 0) {
@@ -204,7 +206,7 @@ int armi_index_create(int device, const uint16_t* rows, int64_t n_rows, int dim,
   }
   const int64_t blocks = (padded + 3) / 4;
   row_norms_kernel<<<dim3((unsigned)blocks), dim3(256), 0, stream>>>(
-      rows, n_rows, padded, dim, idx->norm2, idx->inv_norm, idx->inv_norm32, idx->invalid);
+      rows, 0, n_rows, padded, dim, idx->norm2, idx->inv_norm, idx->inv_norm32, idx->invalid);
   e = hipGetLastError();
   if (e != hipSuccess) { armi_index_destroy(idx); return armi::hip_fail(e, "row_norms_kernel"); }
   auto filt = [&](auto D) {
@@ -224,8 +226,73 @@ int armi_index_create(int device, const uint16_t* rows, int64_t n_rows, int dim,
   return ARMI_OK;
 }
 
+int armi_index_create_tail(int device, int dim, int64_t capacity_rows, int64_t ordinal_base,
+                           armi_index** out, hipStream_t stream) {
+  ARMI_REQUIRE(out != nullptr, "armi_index_create_tail: out is null");
+  *out = nullptr;
+  ARMI_REQUIRE(capacity_rows >= 1 && capacity_rows < (int64_t(1) << 31) - 64,
+               "armi_index_create_tail: capacity_rows must be in [1, 2^31 - 64)");
+  ARMI_REQUIRE(dim == 256 || dim == 512 || dim == 768 || dim == 1024,
+               "armi_index_create_tail: dim must be 256, 512, 768 or 1024");
+  ARMI_HIP(hipSetDevice(device));
+  armi_index* idx = new armi_index();
+  idx->device = device;
+  idx->dim = dim;
+  idx->ordinal_base = ordinal_base;
+  idx->capacity = (capacity_rows + armi::TILE_ROWS - 1) / armi::TILE_ROWS * armi::TILE_ROWS;
+  hipDeviceProp_t prop;
+  hipError_t e = hipGetDeviceProperties(&prop, device);
+  if (e != hipSuccess) { delete idx; return armi::hip_fail(e, "hipGetDeviceProperties"); }
+  idx->num_cus = prop.multiProcessorCount;
+  idx->device_cus = prop.multiProcessorCount;
+  const int64_t cap = idx->capacity;
+  e = hipMalloc(&idx->owned_rows, (size_t)cap * dim * sizeof(uint16_t));
+  idx->rows = idx->owned_rows;
+  if (e == hipSuccess) e = hipMalloc(&idx->norm2, cap * sizeof(int64_t));
+  if (e == hipSuccess) e = hipMalloc(&idx->inv_norm, cap * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc(&idx->inv_norm32, cap * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&idx->invalid, sizeof(unsigned long long));
+  if (e == hipSuccess) e = hipMemsetAsync(idx->invalid, 0, sizeof(unsigned long long), stream);
+  // (the scans read whole tiles: zero rows, not whatever the allocation held)
+  if (e == hipSuccess)
+    e = hipMemsetAsync(idx->owned_rows, 0, (size_t)cap * dim * sizeof(uint16_t), stream);
+  if (e != hipSuccess) { armi_index_destroy(idx); return armi::hip_fail(e, "armi_index_create_tail alloc"); }
+  // every row starts as tile padding
+  row_norms_kernel<<<dim3((unsigned)((cap + 3) / 4)), dim3(256), 0, stream>>>(
+      idx->rows, 0, 0, cap, dim, idx->norm2, idx->inv_norm, idx->inv_norm32, idx->invalid);
+  e = hipGetLastError();
+  if (e != hipSuccess) { armi_index_destroy(idx); return armi::hip_fail(e, "row_norms_kernel"); }
+  *out = idx;
+  return ARMI_OK;
+}
+
+int armi_index_append(armi_index* idx, const uint16_t* rows, int64_t n, hipStream_t stream) {
+  ARMI_REQUIRE(idx != nullptr, "armi_index_append: index is null");
+  ARMI_REQUIRE(idx->capacity > 0, "armi_index_append: not a growable index (armi_index_create_tail)");
+  ARMI_REQUIRE(n >= 0, "armi_index_append: n < 0");
+  if (n == 0) return ARMI_OK;
+  ARMI_REQUIRE(rows != nullptr, "armi_index_append: rows is null");
+  ARMI_REQUIRE(n <= idx->capacity - idx->n_rows, "armi_index_append: past the index's capacity");
+  ARMI_HIP(hipSetDevice(idx->device));
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  ARMI_HIP(hipStreamIsCapturing(stream, &cs));
+  ARMI_REQUIRE(cs == hipStreamCaptureStatusNone, "armi_index_append: the stream is being captured");
+  const int64_t lo = idx->n_rows, hi = lo + n;
+  ARMI_HIP(hipMemcpyAsync(idx->owned_rows + lo * idx->dim, rows, (size_t)n * idx->dim * sizeof(uint16_t),
+                          hipMemcpyDeviceToDevice, stream));
+  row_norms_kernel<<<dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream>>>(
+      idx->rows, lo, hi, hi, idx->dim, idx->norm2, idx->inv_norm, idx->inv_norm32, idx->invalid);
+  ARMI_LAUNCHED("row_norms_kernel(append)");
+  idx->n_rows = hi;
+  idx->n_tiles = (hi + armi::TILE_ROWS - 1) / armi::TILE_ROWS;
+  return ARMI_OK;
+}
+
+int64_t armi_index_capacity(const armi_index* idx) { return idx ? idx->capacity : -1; }
+
 int armi_index_destroy(armi_index* idx) {
   if (!idx) return ARMI_OK;
+  hipFree(idx->owned_rows);
   hipFree(idx->norm2);
   hipFree(idx->inv_norm);
   hipFree(idx->inv_norm32);

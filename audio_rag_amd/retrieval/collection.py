@@ -10,23 +10,51 @@ RetrievalResult carries no id, core/base.py:56-61). The device indexes are rebui
 first search after an add; a built index is read-only, so concurrent searches are safe, and a
 rebuild never frees an index a running search still holds (the old handles die with their last
 reference).
+
+Live ingest (live_tail_rows > 0): after the first build, later upserts are flushed into a small
+growable fp16 segment, the tail (TailIndex + a SparseIndex over the tail's rows only), which
+every search covers together with the main indexes; the main indexes are not touched by a flush.
+When a flush would pass the tail's capacity the tail is folded into new main indexes built from
+device-side concatenations (compact()). A flush changes the tail in place on the current stream:
+searches on other streams must not overlap an upsert's first search.
 """
 
 from __future__ import annotations
 
 import threading
 import weakref
+from collections import namedtuple
 from dataclasses import dataclass, field
 
 import numpy as np
 import torch
 
-from audio_rag_amd.retrieval.device import DenseIndex, SparseIndex
+from audio_rag_amd.retrieval.device import DenseIndex, SparseIndex, TailIndex
 
 BGE_M3_VOCAB = 250002
 
 
 _NO_MATCH = object()
+
+# The device segments of a collection: the main indexes over ordinals [base, base + main_rows)
+# and, in a live collection, the tail over the ordinals behind them (tail None or tail.n_rows == 0:
+# nothing to search there; tail_sparse None in a dense-only collection).
+Segments = namedtuple("Segments", "dense sparse tail tail_sparse main_rows")
+
+
+def mask_words(ok: np.ndarray) -> np.ndarray:
+    """bool [n] -> uint64 bitmask words (bit r of word r // 64 = ok[r]), at least one word."""
+    words = np.zeros(max((len(ok) + 63) // 64, 1), dtype=np.uint64)
+    idx = np.nonzero(ok)[0]
+    np.bitwise_or.at(words, idx >> 6, np.left_shift(np.uint64(1), (idx & 63).astype(np.uint64)))
+    return words
+
+
+def split_mask_words(ok: np.ndarray, main_rows: int) -> tuple[np.ndarray, np.ndarray]:
+    """The per-segment row masks of a live collection: (main, tail) bitmask words of ok[:main_rows]
+    and ok[main_rows:]. Each segment's bit 0 is its own first row, so the tail's words are not a
+    suffix of the whole mask's words unless main_rows is a multiple of 64."""
+    return mask_words(ok[:main_rows]), mask_words(ok[main_rows:])
 
 
 def _canon(x):
@@ -82,6 +110,13 @@ class ChunkCollection:
     # (RetrievalConfig.num_gpus): every rank stages every point on the host and builds device
     # indexes over its contiguous ordinal range only (retrieval/shards.shard_range)
     shard: tuple = (0, 1)
+    # live ingest (RetrievalConfig.live_tail_rows; 0 = rebuild on every add)
+    live_tail_rows: int = 0
+    _tail: TailIndex | None = None
+    _tail_sparse: SparseIndex | None = None
+    _main_rows: int = 0      # points held by the main indexes
+    _vmax: int = -1          # largest sparse term id upserted so far
+    _seg_mask_cache: dict = field(default_factory=dict)
 
     def shard_bounds(self, n: int | None = None) -> tuple[int, int]:
         """[lo, hi) ordinals of this rank's shard of n (default: every) points."""
@@ -113,15 +148,25 @@ class ChunkCollection:
             self.sparse_rows.extend(sparse)
             self.payloads.extend(payloads)
             self._mask_cache.clear()
+            self._seg_mask_cache.clear()
             self._key_index.clear()
+            self._vmax = max([self._vmax] + [int(s[0].max(initial=-1)) for s in sparse
+                                             if s is not None])
 
     # ------------------------------------------------------------------------------- build
+
+    @property
+    def _live(self) -> bool:
+        return self.live_tail_rows > 0 and self.shard[1] == 1 and not self._frozen
 
     def _ensure_built(self) -> None:
         if self._built_rows == self.count:
             return
         with self._lock:
             if self._built_rows == self.count:
+                return
+            if self._live and self._dense is not None and self._built_rows >= 0:
+                self._flush_live()
                 return
             rows = (np.concatenate(self.dense_rows) if self.dense_rows
                     else np.zeros((0, self.dim), dtype=np.float16))
@@ -145,11 +190,144 @@ class ChunkCollection:
                 vocab = max(BGE_M3_VOCAB, vmax + 1)
                 t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
                 self._sparse = SparseIndex(t(indptr), t(idx), t(val), vocab, ordinal_base=lo)
-            self._built_rows = self.count
+            self._built_rows = self._main_rows = self.count
+            self._tail = self._tail_sparse = None
             # The superseded indexes are not closed here: a search that fetched them before
             # this rebuild may still be using them. Dropping the reference frees each one (its
             # __del__ closes it) once the last such search lets go of it.
             del old_dense, old_sparse
+
+    # ------------------------------------------------------------------------- live ingest
+
+    def _upload(self, a: np.ndarray) -> torch.Tensor:
+        return torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+
+    def _host_csr(self, lo: int, hi: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(indptr int64, indices int32, values float32) of points [lo, hi)."""
+        mine = self.sparse_rows[lo:hi]
+        indptr = np.zeros(hi - lo + 1, dtype=np.int64)
+        np.cumsum([0 if s is None else len(s[0]) for s in mine], out=indptr[1:])
+        idx = np.concatenate([s[0] for s in mine if s is not None] or
+                             [np.zeros(0, np.int32)]).astype(np.int32)
+        val = np.concatenate([s[1] for s in mine if s is not None] or
+                             [np.zeros(0, np.float32)]).astype(np.float32)
+        return indptr, idx, val
+
+    def _host_dense(self, lo: int, hi: int) -> np.ndarray:
+        """fp16 rows of points [lo, hi) from the staged blocks (only the blocks they touch)."""
+        out, at = [], 0
+        for blk in self.dense_rows:
+            n = blk.shape[0]
+            if at + n > lo and at < hi:
+                out.append(blk[max(lo - at, 0):hi - at])
+            at += n
+        return np.concatenate(out) if out else np.zeros((0, self.dim), dtype=np.float16)
+
+    def _tail_capacity(self) -> int:
+        # twice the nominal size: a batch that arrives at a nearly full tail still lands in it
+        return 2 * self.live_tail_rows
+
+    def _fold(self, dense_parts: list, csr_parts: list) -> None:
+        """New main indexes over the main rows followed by the given device blocks (fp16 row
+        blocks; (indptr, indices, values) CSRs with indptr starting at 0): device-side
+        concatenations, nothing read from the host staging. The superseded objects die with
+        their last reference."""
+        old = (self._dense, self._sparse)
+        rows = torch.cat([self._dense.rows, *dense_parts]) if dense_parts else self._dense.rows
+        self._dense = DenseIndex(rows, ordinal_base=0)
+        if self.hybrid:
+            sp = old[1]
+            indptr, idx, val = [sp.indptr], [sp.indices], [sp.values]
+            end = sp.indptr[-1:]
+            for p, i, v in csr_parts:
+                indptr.append(p[1:] + end)
+                end = indptr[-1][-1:] if p.numel() > 1 else end
+                idx.append(i)
+                val.append(v)
+            self._sparse = SparseIndex(torch.cat(indptr), torch.cat(idx), torch.cat(val),
+                                       max(BGE_M3_VOCAB, self._vmax + 1), ordinal_base=0)
+        self._main_rows = int(rows.shape[0])
+        self._seg_mask_cache.clear()
+        del old
+
+    def _flush_live(self) -> None:
+        """Brings the points upserted since the last build into the tail (lock held): uploads
+        only their fp16 rows, appends them, and rebuilds the tail's sparse index over the tail's
+        rows. When they would not fit, the tail is folded into the main indexes first (and the new
+        points with it when they alone exceed a tail)."""
+        lo, hi = self._built_rows, self.count
+        self._graphs = {}
+        new = self._upload(self._host_dense(lo, hi))
+        cap = self._tail_capacity()
+        tail_rows = self._tail.n_rows if self._tail is not None else 0
+        if tail_rows + (hi - lo) > cap:
+            dense_parts = list(self._tail.parts) if tail_rows else []
+            csr_parts = []
+            if self.hybrid and tail_rows:
+                ts = self._tail_sparse
+                csr_parts.append((ts.indptr, ts.indices, ts.values))
+            fits = hi - lo <= cap
+            if not fits:
+                dense_parts.append(new)
+                if self.hybrid:
+                    csr_parts.append(tuple(self._upload(a) for a in self._host_csr(lo, hi)))
+            self._fold(dense_parts, csr_parts)
+            self._tail = self._tail_sparse = None
+            if not fits:
+                self._built_rows = hi
+                return
+        if self._tail is None:
+            self._tail = TailIndex(self.dim, cap, self._main_rows, self.device)
+        self._tail.append(new)
+        if self.hybrid:
+            base = self._main_rows
+            indptr, idx, val = (self._upload(a) for a in self._host_csr(base, hi))
+            self._tail_sparse = SparseIndex(indptr, idx, val, max(BGE_M3_VOCAB, self._vmax + 1),
+                                            ordinal_base=base)
+        self._built_rows = hi
+
+    def compact(self) -> None:
+        """Folds the tail into the main indexes now (device-side concatenations; the tail starts
+        empty afterwards). Nothing to do without a tail."""
+        self._ensure_built()
+        with self._lock:
+            if self._tail is None or self._tail.n_rows == 0:
+                return
+            self._graphs = {}
+            csr = []
+            if self.hybrid:
+                ts = self._tail_sparse
+                csr.append((ts.indptr, ts.indices, ts.values))
+            self._fold(list(self._tail.parts), csr)
+            self._tail = self._tail_sparse = None
+
+    def segments(self) -> Segments:
+        """The device segments every search has to cover (see Segments)."""
+        self._ensure_built()
+        with self._lock:
+            return Segments(self._dense, self._sparse, self._tail, self._tail_sparse,
+                            self._main_rows)
+
+    def segment_masks(self, filter_metadata: dict | None):
+        """filter_mask per segment: (main mask, tail mask) device bitmasks, the tail's bit 0 being
+        the tail's first row; None without a filter."""
+        if not filter_metadata:
+            return None
+        seg = self.segments()
+        if seg.tail is None or seg.tail.n_rows == 0:
+            return self.filter_mask(filter_metadata), None
+        key = tuple(sorted((k, repr(v)) for k, v in filter_metadata.items()))
+        cached = self._seg_mask_cache.get(key)
+        if cached is not None and cached[0] == (self.count, seg.main_rows):
+            return cached[1]
+        n = self.count
+        ok = np.ones(n, dtype=bool)
+        for k, v in filter_metadata.items():
+            ok &= self._key_matches(k, v, n)
+        masks = tuple(torch.from_numpy(w.view(np.int64)).to(self.device)
+                      for w in split_mask_words(ok, seg.main_rows))
+        self._seg_mask_cache[key] = ((n, seg.main_rows), masks)
+        return masks
 
     def query_graphs(self) -> dict:
         """The captured single-query searches of the current indexes (key -> graph)."""
@@ -158,12 +336,14 @@ class ChunkCollection:
 
     @property
     def dense_index(self) -> DenseIndex:
-        self._ensure_built()
+        """One index holding every point (a live collection folds its tail in first; live-aware
+        code uses segments())."""
+        self.compact()
         return self._dense
 
     @property
     def sparse_index(self) -> SparseIndex | None:
-        self._ensure_built()
+        self.compact()
         return self._sparse
 
     # ------------------------------------------------------------------------------ filter
@@ -282,8 +462,8 @@ class ChunkCollection:
         for srv in list(self._servers):
             srv.close()
         self._graphs = {}
-        for ix in (self._dense, self._sparse):
+        for ix in (self._dense, self._sparse, self._tail, self._tail_sparse):
             if ix is not None:
                 ix.close()
-        self._dense = self._sparse = None
+        self._dense = self._sparse = self._tail = self._tail_sparse = None
         self._built_rows = -1

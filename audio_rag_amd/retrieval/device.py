@@ -172,6 +172,77 @@ class DenseIndex:
         return out
 
 
+class TailIndex(DenseIndex):
+    """A growable fp16 segment (armi_index_create_tail): the rows added to a live collection
+    since its last compaction. The native index owns its row buffer; `parts` keeps the appended
+    device blocks for the device-side concatenation of a compaction. Every DenseIndex search
+    works on it (fp16 scan forms); tail_topk() is the fused pass that extends a finished list of
+    the main index by this segment's rows."""
+
+    def __init__(self, dim: int, capacity: int, ordinal_base: int, device: torch.device):
+        self.rows = None
+        self.parts: list[torch.Tensor] = []
+        self.dim, self.n_rows = int(dim), 0
+        self.ordinal_base = int(ordinal_base)
+        self.device = device
+        self._handle = ctypes.c_void_p()
+        with torch.cuda.device(device):
+            call("armi_index_create_tail", device.index or 0, self.dim, int(capacity),
+                 self.ordinal_base, ctypes.byref(self._handle), stream_handle())
+        self.capacity = int(query("armi_index_capacity", self._handle))
+
+    def append(self, rows: torch.Tensor) -> None:
+        """Adds fp16 rows [n, dim] behind the current end, ordered on the current stream. Not
+        under graph capture; searches of this index on other streams must not overlap it."""
+        _check_fp16_2d(rows, "rows", self.dim)
+        with torch.cuda.device(self.device):
+            call("armi_index_append", self._handle, ptr(rows), int(rows.shape[0]), stream_handle())
+        self.n_rows = int(query("armi_index_rows", self._handle))
+        if rows.shape[0]:
+            self.parts.append(rows)
+
+    @staticmethod
+    def list_cap() -> int:
+        """Survivors the fused pass keeps per query before it falls back to the exact pass."""
+        return int(query("armi_dense_tail_list_cap"))
+
+    def tail_workspace_bytes(self, n_queries: int, k: int) -> int:
+        return int(query("armi_dense_tail_workspace_bytes", self._handle, n_queries, k))
+
+    def tail_topk(self, queries: torch.Tensor, k: int, main: TopK,
+                  row_mask: torch.Tensor | None = None,
+                  workspace: torch.Tensor | None = None) -> TopK:
+        """The top-k over the main index and this segment, from `main` = the main index's
+        topk(queries, k) (armi_dense_tail_topk). row_mask: bit r = row r of this segment."""
+        _check_fp16_2d(queries, "queries", self.dim)
+        if not 1 <= k <= MAX_K:
+            raise ValueError(f"k must be in [1, {MAX_K}]")
+        b = int(queries.shape[0])
+        if tuple(main.ids.shape) != (b, k):
+            raise ValueError("main must be the main index's top-k of the same queries and k")
+        dev = self.device
+        if row_mask is not None:
+            need = (self.n_rows + 63) // 64
+            if row_mask.dtype != torch.int64 or row_mask.numel() < need or not row_mask.is_cuda:
+                raise ValueError(f"row_mask must be an int64 device tensor of >= {need} words")
+        out = TopK(scores=torch.empty((b, k), dtype=torch.float32, device=dev),
+                   ids=torch.empty((b, k), dtype=torch.int64, device=dev),
+                   rank=torch.empty((b, k), dtype=torch.float64, device=dev),
+                   count=torch.empty(b, dtype=torch.int32, device=dev),
+                   flags=torch.empty(b, dtype=torch.int32, device=dev))
+        if b == 0:
+            return out
+        need = self.tail_workspace_bytes(b, k)
+        if workspace is None or workspace.numel() < need:
+            workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        m_scores, m_ids, m_rank, m_count = (t.contiguous() for t in
+                                            (main.scores, main.ids, main.rank, main.count))
+        call("armi_dense_tail_topk", self._handle, ptr(queries), b, k, ptr(row_mask), ptr(m_scores),
+             ptr(m_ids), ptr(m_rank), ptr(m_count), ptr(out.scores), ptr(out.ids), ptr(out.rank),
+             ptr(out.count), ptr(out.flags), ptr(workspace), workspace.numel(), stream_handle())
+        return out
+
+
 class SparseIndex:
     """The Qdrant sparse vector "sparse" (SparseVectorParams(index=SparseIndexParams(on_disk=
     False)), no IDF modifier) of src/audio_rag/retrieval/qdrant.py:103-107, as a CSR in HBM.

@@ -92,7 +92,7 @@ class _QueryGraph:
 
     def __init__(self, ret: "MI355XRetriever", coll: ChunkCollection, mode: str, top_k: int):
         dev, dim = ret.device, coll.dim
-        self.indexes = (coll.dense_index, coll.sparse_index)  # the graph's kernels read them
+        self.indexes = coll.segments()  # the graph's kernels read them
         self.mode, self.k, self.dim = mode, top_k, dim
         self.lock = threading.Lock()
         off_ptr = dim * 2
@@ -202,6 +202,7 @@ class MI355XRetriever(BaseRetriever):
         try:
             coll = ChunkCollection(resolved, self.embedding_dim, hybrid, self.device)
             coll.shard = (self._rank, self._world)
+            coll.live_tail_rows = self.config.live_tail_rows
             self._collections[resolved] = coll
             logger.info(f"Creating {'hybrid' if hybrid else 'dense'} collection: {resolved}")
             return resolved
@@ -301,6 +302,7 @@ class MI355XRetriever(BaseRetriever):
             resolved = collection_name or read_meta(path)["name"]
             coll = ChunkCollection.load(path, self.device, resolved)
             coll.shard = (self._rank, self._world)
+            coll.live_tail_rows = self.config.live_tail_rows
         except Exception as e:
             raise RetrievalError(f"Failed to load chunk store '{path}': {e}")
         old = self._collections.pop(resolved, None)
@@ -329,10 +331,11 @@ class MI355XRetriever(BaseRetriever):
         search_type = search_type or self.config.search_type
         coll = self._collections[resolved]
         mode = self._mode(coll, search_type, queries.has_sparse)
-        mask = coll.filter_mask(filter_metadata)
         if self._world > 1:
+            mask = coll.filter_mask(filter_metadata)
             return self._search_sharded(coll, queries, top_k, mode, mask, filter_metadata), mode
-        return self._search_device(coll, queries, top_k, mode, mask), mode
+        return self._search_device(coll, queries, top_k, mode,
+                                   coll.segment_masks(filter_metadata)), mode
 
     def _search_sharded(self, coll: ChunkCollection, queries: QueryBatch, top_k: int, mode: str,
                         mask: torch.Tensor | None, mask_spec: dict | None = None) -> TopK:
@@ -367,21 +370,43 @@ class MI355XRetriever(BaseRetriever):
             raise RetrievalError(str(e))
 
     def _search_device(self, coll: ChunkCollection, queries: QueryBatch, top_k: int, mode: str,
-                       mask: torch.Tensor | None) -> TopK:
-        """The device work of search_batch for a resolved collection and branch."""
+                       masks: tuple | None) -> TopK:
+        """The device work of search_batch for a resolved collection and branch. masks:
+        ChunkCollection.segment_masks (main mask, tail mask) or None. Both segments of a live
+        collection are searched: dense by the main top-k followed by the fused tail pass, sparse
+        by both indexes' top-k merged exactly (rank = score, as the sharded search merges); an
+        empty tail adds no kernel."""
+        from audio_rag_amd.retrieval.device import merge_shards
+
+        seg = coll.segments()
+        mask, tmask = masks if masks is not None else (None, None)
+        live = seg.tail is not None and seg.tail.n_rows > 0
+        sq = (queries.sparse_indptr, queries.sparse_indices, queries.sparse_values)
+
+        def dense(k: int) -> TopK:
+            d = seg.dense.topk(queries.dense, k, row_mask=mask)
+            return seg.tail.tail_topk(queries.dense, k, d, row_mask=tmask) if live else d
+
+        def sparse(k: int) -> TopK:
+            s = seg.sparse.topk(*sq, k, row_mask=mask)
+            if not live:
+                return s
+            t = seg.tail_sparse.topk(*sq, k, row_mask=tmask)
+            scores = torch.stack([s.scores, t.scores])
+            m = merge_shards(scores.double(), scores, torch.stack([s.ids, t.ids]),
+                             torch.stack([s.count, t.count]), k)
+            m.flags = s.flags
+            return m
+
         if mode == "hybrid":
             if self._hybrid is None:
                 self._hybrid = ConcurrentHybrid(self.device)
-            sq = (queries.sparse_indptr, queries.sparse_indices, queries.sparse_values)
-            fused = self._hybrid(
-                lambda: coll.dense_index.topk(queries.dense, 2 * top_k, row_mask=mask),
-                lambda: coll.sparse_index.topk(*sq, 2 * top_k, row_mask=mask),
-                sq + ((mask,) if mask is not None else ()), top_k, rrf_k=self.config.rrf_k)
-            return fused
+            extra = tuple(m for m in (mask, tmask) if m is not None)
+            return self._hybrid(lambda: dense(2 * top_k), lambda: sparse(2 * top_k), sq + extra,
+                                top_k, rrf_k=self.config.rrf_k)
         if mode == "sparse":
-            return coll.sparse_index.topk(queries.sparse_indptr, queries.sparse_indices,
-                                          queries.sparse_values, top_k, row_mask=mask)
-        return coll.dense_index.topk(queries.dense, top_k, row_mask=mask)
+            return sparse(top_k)
+        return dense(top_k)
 
     def to_query_batch(self, query_embeddings: list[EmbeddingResult]) -> QueryBatch:
         dense = torch.from_numpy(fp16_rows([q.dense for q in query_embeddings],

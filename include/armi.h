@@ -32,7 +32,8 @@
  *   - Every launch is asynchronous and ordered on the given stream; nothing synchronises the
  *     host (graph capture safe). Workspaces are caller-allocated (see *_workspace_bytes).
  *   - An index is immutable after armi_index_create returns; any number of streams may search
- *     one index concurrently, each with its own workspace.
+ *     one index concurrently, each with its own workspace. (A growable index changes only in
+ *     armi_index_append; see its contract.)
  *   - fp16 values are passed as their IEEE binary16 bit patterns (uint16_t).
  */
 #ifndef ARMI_H
@@ -54,8 +55,9 @@ extern "C" {
 /* ABI history. 1: rounds 1-3. 2 (round 5): armi_enc_cls_head_sigmoid takes the dense weight
  * transposed ([in][out], was [out][in]); armi_dense_topk_ex / _first / _second_pass,
  * armi_index_set_scan_cus and armi_cu_split_streams removed. A caller built against version 1
- * must not bind this library (armi_abi_version() tells). */
-#define ARMI_ABI_VERSION 2
+ * must not bind this library (armi_abi_version() tells). 3: growable fp16 segments
+ * (armi_index_create_tail / _append / _capacity) and armi_dense_tail_topk; nothing removed. */
+#define ARMI_ABI_VERSION 3
 
 /* flags written per query by the top-k entry points */
 #define ARMI_FLAG_CERTIFIED 1u /* fast path proved its top-k equal to the exact ranking */
@@ -96,6 +98,31 @@ int64_t armi_index_invalid_rows(const armi_index* index);
  * of the quantisation error per row; the scans read it for k <= 64 (armi_dense_scan_form). */
 int armi_index_norms(const armi_index* index, const int64_t** norm2, const double** inv_norm,
                      const float** inv_norm32);
+
+/* A growable fp16 segment (the "tail" of a live collection): an index that owns its row buffer,
+ * starts empty and takes rows by armi_index_append. capacity_rows is rounded up to whole 32-row
+ * tiles (armi_index_capacity tells); the norm arrays are sized for the capacity and rows past
+ * armi_index_rows() are padding (norm2 = -1, inv_norm = 0, inv_norm32 = NaN). The segment keeps no
+ * int8 filter image: armi_dense_topk runs its fp16 scan forms over it (armi_dense_scan_form never
+ * reports an int8 form) and answers uncertified queries by the exhaustive exact pass, with the
+ * same exact ranking. armi_index_rows / _norms / _invalid_rows / _destroy, armi_dense_topk and
+ * armi_dense_exact_topk take it like any index; workspace sizes depend on the current row count,
+ * so ask for them after an append. */
+int armi_index_create_tail(int device, int dim, int64_t capacity_rows, int64_t ordinal_base,
+                           armi_index** out, hipStream_t stream);
+/* Appends n fp16 rows (device memory, same component rule as armi_index_create; violating rows
+ * count in armi_index_invalid_rows and score as -inf) behind the current end: copies them into the
+ * index's buffer and computes their exact norms. Past the capacity the call fails and changes
+ * nothing. Contract:
+ *   - stream-ordered: the copy and the norms run on `stream`; searches enqueued on that stream
+ *     afterwards see the new rows;
+ *   - it must not run under stream capture (it changes host-side state: the call refuses a
+ *     capturing stream), and a graph captured over the index before an append must be dropped
+ *     (the row count is a launch argument);
+ *   - the caller keeps searches of the same index on other streams from overlapping an append. */
+int armi_index_append(armi_index* index, const uint16_t* rows, int64_t n, hipStream_t stream);
+/* Row capacity of a growable index (whole tiles); 0 for an armi_index_create index. */
+int64_t armi_index_capacity(const armi_index* index);
 
 /* The scan armi_dense_topk runs for n_queries queries and top-k (for roofline accounting):
  *   ARMI_SCAN_FP16         64-query scan over the fp16 rows (2 B per component)
@@ -138,6 +165,29 @@ int armi_dense_topk(const armi_index* index, const uint16_t* queries, int n_quer
                     const uint64_t* row_mask, float* out_scores, int64_t* out_ids,
                     double* out_rank, int32_t* out_count, uint32_t* out_flags,
                     void* workspace, size_t workspace_bytes, hipStream_t stream);
+
+/* Global top-k over a main index and a growable tail, given the main index's finished list
+ * (armi_dense_topk's outputs for the same queries and k: main_* are [n_queries][k] / [n_queries]).
+ * The main list's k-th exact key bounds the global k-th from below, so only tail rows whose
+ * approximate key (the fp16 MFMA scan's, within delta = 4 dim 2^-24 |q| of the exact key) reaches
+ * that key minus delta can matter: the scan appends those (row, query) pairs to per-query lists of
+ * armi_dense_tail_list_cap() entries, and one workgroup per query rescores its list exactly and
+ * merges it with the main list by (key desc, ordinal asc). A query whose list overflows (or whose
+ * main list holds fewer than k entries over a tail larger than the list) is answered from the
+ * exact keys of every tail row and flagged ARMI_FLAG_FALLBACK; the others ARMI_FLAG_CERTIFIED.
+ * Outputs follow armi_dense_topk's conventions (out_rank nullable; -1 / -inf past the count) and
+ * must not alias the main lists. tail_row_mask: nullable, bit r = row r of the tail. Masked,
+ * invalid and padding rows never appear. No host synchronisation; graph-capture safe.
+ * ARMI_TAIL_PASS=general in the environment (read per call) computes the same result by
+ * armi_dense_topk over the tail and armi_topk_merge_shards (A/B runs and tests). */
+size_t armi_dense_tail_workspace_bytes(const armi_index* tail, int n_queries, int k);
+int armi_dense_tail_list_cap(void);
+int armi_dense_tail_topk(const armi_index* tail, const uint16_t* queries, int n_queries, int k,
+                         const uint64_t* tail_row_mask, const float* main_scores,
+                         const int64_t* main_ids, const double* main_rank,
+                         const int32_t* main_count, float* out_scores, int64_t* out_ids,
+                         double* out_rank, int32_t* out_count, uint32_t* out_flags,
+                         void* workspace, size_t workspace_bytes, hipStream_t stream);
 
 size_t armi_dense_exact_workspace_bytes(const armi_index* index, int n_queries, int k);
 /* Exhaustive exact scan with the same outputs and ranking as armi_dense_topk. */
