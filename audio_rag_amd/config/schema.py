@@ -67,6 +67,13 @@ class RetrievalConfig(BaseModel):
     # points. 0: every add rebuilds the indexes on the next search. Ignored (rebuild) with
     # num_gpus > 1 and for collections built from device indexes
     live_tail_rows: int = Field(default=0, ge=0)
+    # selective filters: > 0 lets a filtered search whose filter matches at most this many rows
+    # rank those rows directly (armi_*_rowlist_topk) instead of scanning the whole index under a
+    # row mask, when that reads no more bytes than the scan (2 * queries * matches <= rows), and
+    # lets the queries of one batch carry different filters through one launch. 0: every filtered
+    # search is a masked scan, one per filter. Answers are the same either way. Ignored with
+    # num_gpus > 1
+    filter_list_rows: int = Field(default=0, ge=0)
 
 
 class RerankingConfig(BaseModel):

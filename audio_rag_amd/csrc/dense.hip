@@ -3072,6 +3072,169 @@ TailWorkspace carve_tail(void* base, const armi_index* tail, int nq, int k) {
   return w;
 }
 
+// ------------------------------------------------------------------------ row-list top-k
+// armi_dense_rowlist_topk: the exact ranking of given rows (a selective metadata filter's matches)
+// instead of a masked scan of the whole index. Grid (chunks, queries): workgroup (c, q) scores rows
+// [c * kRowlistChunk, ...) of query q's list exactly (exact_keys8, eight rows per wave and round),
+// sorts them and keeps the chunk's top k. A call whose longest list fits one chunk writes the
+// outputs from that workgroup (`direct`); otherwise the chunk lists go to the workspace
+// ([query][chunk][k]) and dense_rowlist_merge_kernel, one workgroup per query, merges them.
+constexpr int kRowlistChunk = kColChunk;
+constexpr size_t kRowlistLds = 2 * kRowlistChunk * 16;
+
+// The top k of key / ord (sorted) as the call's outputs for query qg, by wave 0.
+__device__ __forceinline__ void rowlist_write_out(const double* key, const int64_t* ord, int qg,
+                                                  int k, double iq, float* __restrict__ out_scores,
+                                                  int64_t* __restrict__ out_ids,
+                                                  double* __restrict__ out_rank,
+                                                  int32_t* __restrict__ out_count,
+                                                  uint32_t* __restrict__ out_flags) {
+  const int lane = threadIdx.x & 63;
+  if (armi::wave_id() != 0) return;
+  int n_valid = 0;
+  for (int c = lane; c < k; c += 64) n_valid += ord[c] != kNoOrd;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) n_valid += armi::xor_stride(n_valid, off);
+  for (int c = lane; c < k; c += 64) {
+    const size_t o = (size_t)qg * k + c;
+    const bool v = ord[c] != kNoOrd;
+    out_scores[o] = v ? (float)(key[c] * iq) : kNegInf;
+    out_ids[o] = v ? ord[c] : -1;
+    if (out_rank) out_rank[o] = v ? key[c] : kNegInfD;
+  }
+  if (lane == 0) {
+    out_count[qg] = n_valid;
+    out_flags[qg] = ARMI_FLAG_ROWLIST;
+  }
+}
+
+// 1 / |q| of the 2^24-scaled query, the merge kernels' arithmetic (query_norms_kernel).
+template <int DIM>
+__device__ __forceinline__ double rowlist_inv_q(const int32_t (&qf)[DIM / 64]) {
+  int64_t n2q = 0;
+#pragma unroll
+  for (int i = 0; i < DIM / 64; ++i) n2q += (int64_t)qf[i] * (int64_t)qf[i];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) n2q += armi::xor_stride(n2q, off);
+  return n2q > 0 ? 1.0 / sqrt((double)n2q) : 0.0;
+}
+
+template <int DIM>
+__global__ __launch_bounds__(kDenseMergeThreads) void dense_rowlist_chunk_kernel(
+    const uint16_t* __restrict__ rows, const double* __restrict__ inv_norm,
+    const int64_t* __restrict__ norm2, int64_t n_rows, const uint16_t* __restrict__ queries, int k,
+    int64_t ordinal_base, const int64_t* __restrict__ list_ptr,
+    const int32_t* __restrict__ list_rows, const int32_t* __restrict__ q_list,
+    int n_lists, int64_t max_list_rows, int direct,
+    double* __restrict__ part_key, int64_t* __restrict__ part_ord, float* __restrict__ out_scores,
+    int64_t* __restrict__ out_ids, double* __restrict__ out_rank, int32_t* __restrict__ out_count,
+    uint32_t* __restrict__ out_flags) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  double* key = reinterpret_cast<double*>(smem);                           // [kRowlistChunk]
+  int64_t* ord = reinterpret_cast<int64_t*>(smem + kRowlistChunk * 8);      // [kRowlistChunk]
+  const int qg = blockIdx.y;
+  const int chunk = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = armi::wave_id();
+  const int l = q_list[qg];
+  const bool listed = l >= 0 && l < n_lists;  // a query naming no list ranks nothing
+  const int64_t lo = listed ? list_ptr[l] : 0;
+  const int64_t len = listed ? min<int64_t>(list_ptr[l + 1] - lo, max_list_rows) : 0;
+  const int64_t c0 = (int64_t)chunk * kRowlistChunk;
+  // past the list's end (workgroup-uniform); an empty list's answer comes from chunk 0 (direct)
+  // or from the merge kernel
+  if (c0 >= len && !(direct && chunk == 0)) return;
+  const int m = (int)max<int64_t>(0, min<int64_t>(kRowlistChunk, len - c0));
+  int32_t qf[DIM / 64];
+  load_fixed<DIM>(queries + (size_t)qg * DIM, lane, qf);
+  constexpr int kPerWave = kRowlistChunk / (kDenseMergeThreads / 64);  // 64 entries per wave
+  for (int b = 0; b < kPerWave; b += 8) {
+    const int e0 = kPerWave * wave + b;
+    double kk = kNegInfD;
+    int32_t myrow = -1;
+    if (e0 < m) {  // wave-uniform
+      int32_t rr[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        int32_t o = -1;
+        if (e0 + j < m) {
+          const int32_t r = list_rows[lo + c0 + e0 + j];
+          // rows outside the index or outside the fp16 domain never rank
+          if (r >= 0 && r < n_rows && norm2[r] >= 0) o = r;
+        }
+        rr[j] = o;
+      }
+      exact_keys8<DIM>(qf, rows, inv_norm, rr, lane, kk, myrow);
+    }
+    if ((lane & 7) == 0) {
+      const int e = e0 + ((lane >> 3) & 7);
+      key[e] = myrow >= 0 ? kk : kNegInfD;
+      ord[e] = myrow >= 0 ? ordinal_base + myrow : kNoOrd;
+    }
+  }
+  armi::lds_sort_rank_desc(key, ord, armi::pow2_at_least(m > k ? m : k));
+  if (direct) {
+    rowlist_write_out(key, ord, qg, k, rowlist_inv_q<DIM>(qf), out_scores, out_ids, out_rank,
+                      out_count, out_flags);
+    return;
+  }
+  const size_t base = ((size_t)qg * gridDim.x + chunk) * k;
+  for (int c = tid; c < k; c += kDenseMergeThreads) {
+    part_key[base + c] = key[c];
+    part_ord[base + c] = ord[c];
+  }
+}
+
+// One workgroup per query: the chunk lists of its row list (ceil(len / kRowlistChunk) lists of k
+// sorted entries, empty slots ordinal kNoOrd) through LDS, [0, kRowlistChunk) the best so far,
+// [kRowlistChunk, 2 kRowlistChunk) the next entries, one bitonic sort per round.
+template <int DIM>
+__global__ __launch_bounds__(kDenseMergeThreads) void dense_rowlist_merge_kernel(
+    const double* __restrict__ part_key, const int64_t* __restrict__ part_ord, int chunks_max,
+    const uint16_t* __restrict__ queries, int k, const int64_t* __restrict__ list_ptr,
+    const int32_t* __restrict__ q_list, int n_lists, int64_t max_list_rows,
+    float* __restrict__ out_scores,
+    int64_t* __restrict__ out_ids, double* __restrict__ out_rank, int32_t* __restrict__ out_count,
+    uint32_t* __restrict__ out_flags) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  double* key = reinterpret_cast<double*>(smem);                             // [2 * kRowlistChunk]
+  int64_t* ord = reinterpret_cast<int64_t*>(smem + 2 * kRowlistChunk * 8);    // [2 * kRowlistChunk]
+  const int qg = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int l = q_list[qg];
+  const int64_t len =
+      l >= 0 && l < n_lists ? min<int64_t>(list_ptr[l + 1] - list_ptr[l], max_list_rows) : 0;
+  const int64_t chunks =
+      min<int64_t>(chunks_max, (max<int64_t>(len, 0) + kRowlistChunk - 1) / kRowlistChunk);
+  const int64_t total = chunks * k;  // entries [0, total) of the query's chunk lists
+  const double* pk = part_key + (size_t)qg * chunks_max * k;
+  const int64_t* po = part_ord + (size_t)qg * chunks_max * k;
+  for (int e = tid; e < 2 * kRowlistChunk; e += kDenseMergeThreads) {
+    key[e] = kNegInfD;
+    ord[e] = kNoOrd;
+  }
+  for (int64_t t0 = 0; t0 < total; t0 += kRowlistChunk) {
+    __syncthreads();  // the previous sort is done with [kRowlistChunk, 2 kRowlistChunk)
+    for (int e = tid; e < kRowlistChunk; e += kDenseMergeThreads) {
+      const bool v = t0 + e < total;
+      key[kRowlistChunk + e] = v ? pk[t0 + e] : kNegInfD;
+      ord[kRowlistChunk + e] = v ? po[t0 + e] : kNoOrd;
+    }
+    armi::lds_sort_rank_desc(key, ord, 2 * kRowlistChunk);
+  }
+  __syncthreads();
+  int32_t qf[DIM / 64];
+  load_fixed<DIM>(queries + (size_t)qg * DIM, lane, qf);
+  rowlist_write_out(key, ord, qg, k, rowlist_inv_q<DIM>(qf), out_scores, out_ids, out_rank,
+                    out_count, out_flags);
+}
+
+int rowlist_chunks(int64_t max_list_rows) {
+  return (int)std::max<int64_t>(1, (max_list_rows + kRowlistChunk - 1) / kRowlistChunk);
+}
+
 template <typename F>
 int dispatch_dim(int dim, F&& f) {
   switch (dim) {
@@ -3237,6 +3400,60 @@ int armi_dense_tail_topk(const armi_index* tail, const uint16_t* queries, int n_
         tail_row_mask, tail->n_rows, queries, k, tail->ordinal_base, main_ids, main_rank,
         main_count, out_scores, out_ids, out_rank, out_count, out_flags);
     ARMI_LAUNCHED("dense_tail_finish_kernel");
+    return ARMI_OK;
+  });
+}
+
+size_t armi_dense_rowlist_workspace_bytes(const armi_index* idx, int n_queries, int k,
+                                          int64_t max_list_rows) {
+  if (!idx || n_queries <= 0 || k <= 0 || max_list_rows < 0) return 0;
+  k = std::min(k, kMaxK);
+  const int chunks = rowlist_chunks(max_list_rows);
+  if (chunks == 1) return 256;  // one chunk per list: the chunk workgroups write the outputs
+  return 2 * armi::align_up((size_t)n_queries * chunks * k * 8, 256) + 256;
+}
+
+int armi_dense_rowlist_topk(const armi_index* idx, const uint16_t* queries, int n_queries, int k,
+                            const int64_t* list_ptr, const int32_t* list_rows,
+                            const int32_t* q_list, int n_lists, int64_t max_list_rows,
+                            float* out_scores, int64_t* out_ids, double* out_rank,
+                            int32_t* out_count, uint32_t* out_flags, void* workspace,
+                            size_t workspace_bytes, hipStream_t stream) {
+  ARMI_REQUIRE(idx != nullptr, "armi_dense_rowlist_topk: index is null");
+  ARMI_REQUIRE(n_queries >= 0 && n_queries <= 65535,
+               "armi_dense_rowlist_topk: n_queries must be in [0, 65535]");
+  ARMI_REQUIRE(k >= 1 && k <= kMaxK, "armi_dense_rowlist_topk: k must be in [1, 240]");
+  ARMI_REQUIRE(n_lists >= 1, "armi_dense_rowlist_topk: n_lists < 1");
+  ARMI_REQUIRE(max_list_rows >= 0 && max_list_rows <= idx->n_rows,
+               "armi_dense_rowlist_topk: max_list_rows must be in [0, rows of the index]");
+  if (n_queries == 0) return ARMI_OK;
+  // (list_rows may be null when every list is empty)
+  ARMI_REQUIRE(queries && list_ptr && q_list && (list_rows || max_list_rows == 0) && out_scores &&
+                   out_ids && out_count && out_flags && workspace,
+               "armi_dense_rowlist_topk: null pointer argument");
+  ARMI_REQUIRE(workspace_bytes >=
+                   armi_dense_rowlist_workspace_bytes(idx, n_queries, k, max_list_rows),
+               "armi_dense_rowlist_topk: workspace too small");
+  ARMI_HIP(hipSetDevice(idx->device));
+  const int nq = n_queries;
+  const int chunks = rowlist_chunks(max_list_rows);
+  const int direct = chunks == 1;
+  armi::Carver cv(workspace);
+  double* part_key = cv.take<double>(direct ? 0 : (size_t)nq * chunks * k);
+  int64_t* part_ord = cv.take<int64_t>(direct ? 0 : (size_t)nq * chunks * k);
+  return dispatch_dim(idx->dim, [&](auto D) {
+    constexpr int DIM = decltype(D)::value;
+    dense_rowlist_chunk_kernel<DIM><<<dim3(chunks, nq), dim3(kDenseMergeThreads), kRowlistLds / 2,
+                                      stream>>>(
+        idx->rows, idx->inv_norm, idx->norm2, idx->n_rows, queries, k, idx->ordinal_base, list_ptr,
+        list_rows, q_list, n_lists, max_list_rows, direct, part_key, part_ord, out_scores, out_ids,
+        out_rank, out_count, out_flags);
+    ARMI_LAUNCHED("dense_rowlist_chunk_kernel");
+    if (direct) return ARMI_OK;
+    dense_rowlist_merge_kernel<DIM><<<dim3(nq), dim3(kDenseMergeThreads), kRowlistLds, stream>>>(
+        part_key, part_ord, chunks, queries, k, list_ptr, q_list, n_lists, max_list_rows,
+        out_scores, out_ids, out_rank, out_count, out_flags);
+    ARMI_LAUNCHED("dense_rowlist_merge_kernel");
     return ARMI_OK;
   });
 }

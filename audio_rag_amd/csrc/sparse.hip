@@ -1865,9 +1865,199 @@ __global__ __launch_bounds__(kUnpackThreads) void query_slots_unpack_kernel(
   }
 }
 
+// ------------------------------------------------------------------------ row-list top-k
+// armi_sparse_rowlist_topk: the exact ranking of given rows (a selective metadata filter's matches)
+// from the forward CSR, without the inverted index. Grid (chunks, queries): workgroup (c, q)
+// scores rows [c * kRlChunk, ...) of query q's list, one row per thread and round, by the merge
+// join of the row's and the query's ascending term ids (the products rounded, then added in that
+// order: the exact scan's and the oracle's arithmetic), sorts the rows that share a term and keeps
+// the chunk's top k. A call whose longest list fits one chunk writes the outputs from that
+// workgroup (`direct`); otherwise the chunk lists go to the workspace ([query][chunk][k]) and
+// sparse_rowlist_merge_kernel, one workgroup per query, merges them.
+constexpr int kRlChunk = 512;
+constexpr int kRlThreads = 256;
+constexpr double kRlNegInf = -std::numeric_limits<double>::infinity();
+constexpr int64_t kRlNoOrd = std::numeric_limits<int64_t>::max();
+
+// The top k of key / ord (sorted) as the call's outputs for query q (k <= kRlThreads).
+__device__ __forceinline__ void rowlist_write_out(const double* key, const int64_t* ord, int q,
+                                                  int k, float* __restrict__ out_scores,
+                                                  int64_t* __restrict__ out_ids,
+                                                  int32_t* __restrict__ out_count,
+                                                  uint32_t* __restrict__ out_flags) {
+  const int tid = threadIdx.x;
+  const bool v = tid < k && ord[tid] != kRlNoOrd;
+  const int n_valid = __syncthreads_count(v);
+  if (tid < k) {
+    const size_t o = (size_t)q * k + tid;
+    out_scores[o] = v ? (float)key[tid] : kNegInf;
+    out_ids[o] = v ? ord[tid] : -1;
+  }
+  if (tid == 0) {
+    out_count[q] = n_valid;
+    out_flags[q] = ARMI_FLAG_ROWLIST;
+  }
+}
+
+__global__ __launch_bounds__(kRlThreads) void sparse_rowlist_chunk_kernel(
+    const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
+    const float* __restrict__ values, int64_t n_rows, int64_t ordinal_base,
+    const int32_t* __restrict__ q_indptr, const int32_t* __restrict__ q_indices,
+    const float* __restrict__ q_values, int k, const int64_t* __restrict__ list_ptr,
+    const int32_t* __restrict__ list_rows, const int32_t* __restrict__ q_list,
+    int n_lists, int64_t max_list_rows, int direct,
+    double* __restrict__ part_key, int64_t* __restrict__ part_ord, float* __restrict__ out_scores,
+    int64_t* __restrict__ out_ids, int32_t* __restrict__ out_count,
+    uint32_t* __restrict__ out_flags) {
+  __shared__ double key[kRlChunk];
+  __shared__ int64_t ord[kRlChunk];
+  const int q = blockIdx.y;
+  const int chunk = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int l = q_list[q];
+  const bool listed = l >= 0 && l < n_lists;  // a query naming no list ranks nothing
+  const int64_t lo = listed ? list_ptr[l] : 0;
+  const int64_t len = listed ? min<int64_t>(list_ptr[l + 1] - lo, max_list_rows) : 0;
+  const int64_t c0 = (int64_t)chunk * kRlChunk;
+  // past the list's end (workgroup-uniform); an empty list's answer comes from chunk 0 (direct)
+  // or from the merge kernel
+  if (c0 >= len && !(direct && chunk == 0)) return;
+  const int m = (int)max<int64_t>(0, min<int64_t>(kRlChunk, len - c0));
+  const int32_t qa = q_indptr[q], qb = q_indptr[q + 1];
+  for (int e = tid; e < kRlChunk; e += kRlThreads) {
+    double kk = kRlNegInf;
+    int64_t oo = kRlNoOrd;
+    if (e < m) {
+      const int32_t r = list_rows[lo + c0 + e];
+      if (r >= 0 && r < n_rows) {
+        int64_t i = indptr[r];
+        const int64_t ie = indptr[r + 1];
+        int32_t j = qa;
+        float s = 0.0f;
+        bool hit = false;
+        while (i < ie && j < qb) {
+          const int32_t ti = indices[i], tj = q_indices[j];
+          if (ti == tj) {
+            s = __fadd_rn(s, __fmul_rn(q_values[j], values[i]));
+            hit = true;
+          }
+          i += ti <= tj;
+          j += tj <= ti;
+        }
+        if (hit) {  // a shared term ranks the row, whatever its score
+          kk = (double)s;
+          oo = ordinal_base + r;
+        }
+      }
+    }
+    key[e] = kk;
+    ord[e] = oo;
+  }
+  armi::lds_sort_rank_desc(key, ord, armi::pow2_at_least(m > k ? m : k));
+  if (direct) {
+    rowlist_write_out(key, ord, q, k, out_scores, out_ids, out_count, out_flags);
+    return;
+  }
+  const size_t base = ((size_t)q * gridDim.x + chunk) * k;
+  for (int c = tid; c < k; c += kRlThreads) {
+    part_key[base + c] = key[c];
+    part_ord[base + c] = ord[c];
+  }
+}
+
+// One workgroup per query: the chunk lists of its row list through LDS, [0, kRlChunk) the best so
+// far, [kRlChunk, 2 kRlChunk) the next entries, one bitonic sort per round.
+__global__ __launch_bounds__(kRlThreads) void sparse_rowlist_merge_kernel(
+    const double* __restrict__ part_key, const int64_t* __restrict__ part_ord, int chunks_max,
+    int k, const int64_t* __restrict__ list_ptr, const int32_t* __restrict__ q_list,
+    int n_lists, int64_t max_list_rows, float* __restrict__ out_scores,
+    int64_t* __restrict__ out_ids, int32_t* __restrict__ out_count,
+    uint32_t* __restrict__ out_flags) {
+  __shared__ double key[2 * kRlChunk];
+  __shared__ int64_t ord[2 * kRlChunk];
+  const int q = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int l = q_list[q];
+  const int64_t len =
+      l >= 0 && l < n_lists ? min<int64_t>(list_ptr[l + 1] - list_ptr[l], max_list_rows) : 0;
+  const int64_t chunks = min<int64_t>(chunks_max, (max<int64_t>(len, 0) + kRlChunk - 1) / kRlChunk);
+  const int64_t total = chunks * k;
+  const double* pk = part_key + (size_t)q * chunks_max * k;
+  const int64_t* po = part_ord + (size_t)q * chunks_max * k;
+  for (int e = tid; e < 2 * kRlChunk; e += kRlThreads) {
+    key[e] = kRlNegInf;
+    ord[e] = kRlNoOrd;
+  }
+  for (int64_t t0 = 0; t0 < total; t0 += kRlChunk) {
+    __syncthreads();  // the previous sort is done with [kRlChunk, 2 kRlChunk)
+    for (int e = tid; e < kRlChunk; e += kRlThreads) {
+      const bool v = t0 + e < total;
+      key[kRlChunk + e] = v ? pk[t0 + e] : kRlNegInf;
+      ord[kRlChunk + e] = v ? po[t0 + e] : kRlNoOrd;
+    }
+    armi::lds_sort_rank_desc(key, ord, 2 * kRlChunk);
+  }
+  __syncthreads();
+  rowlist_write_out(key, ord, q, k, out_scores, out_ids, out_count, out_flags);
+}
+
+int rowlist_chunks(int64_t max_list_rows) {
+  return (int)std::max<int64_t>(1, (max_list_rows + kRlChunk - 1) / kRlChunk);
+}
+
 }  // namespace
 
 extern "C" {
+
+size_t armi_sparse_rowlist_workspace_bytes(int n_queries, int k, int64_t max_list_rows) {
+  if (n_queries <= 0 || k <= 0 || max_list_rows < 0) return 0;
+  k = std::min(k, kMaxK);
+  const int chunks = rowlist_chunks(max_list_rows);
+  if (chunks == 1) return 256;  // one chunk per list: the chunk workgroups write the outputs
+  return 2 * armi::align_up((size_t)n_queries * chunks * k * 8, 256) + 256;
+}
+
+int armi_sparse_rowlist_topk(const int64_t* indptr, const int32_t* indices, const float* values,
+                             int64_t n_rows, int64_t ordinal_base, const int32_t* q_indptr,
+                             const int32_t* q_indices, const float* q_values, int n_queries, int k,
+                             const int64_t* list_ptr, const int32_t* list_rows,
+                             const int32_t* q_list, int n_lists, int64_t max_list_rows,
+                             float* out_scores, int64_t* out_ids, int32_t* out_count,
+                             uint32_t* out_flags, void* workspace, size_t workspace_bytes,
+                             hipStream_t stream) {
+  ARMI_REQUIRE(n_rows >= 0, "armi_sparse_rowlist_topk: n_rows < 0");
+  ARMI_REQUIRE(n_queries >= 0 && n_queries <= 65535,
+               "armi_sparse_rowlist_topk: n_queries must be in [0, 65535]");
+  ARMI_REQUIRE(k >= 1 && k <= kMaxK, "armi_sparse_rowlist_topk: k must be in [1, 240]");
+  ARMI_REQUIRE(n_lists >= 1, "armi_sparse_rowlist_topk: n_lists < 1");
+  ARMI_REQUIRE(max_list_rows >= 0 && max_list_rows <= n_rows,
+               "armi_sparse_rowlist_topk: max_list_rows must be in [0, n_rows]");
+  if (n_queries == 0) return ARMI_OK;
+  // (the CSR value arrays may be null for a corpus without postings, list_rows when every list
+  // is empty, the query term arrays are not read for queries without terms)
+  ARMI_REQUIRE((indptr || max_list_rows == 0) && q_indptr && list_ptr && q_list &&
+                   (list_rows || max_list_rows == 0) && out_scores && out_ids && out_count &&
+                   out_flags && workspace,
+               "armi_sparse_rowlist_topk: null pointer argument");
+  ARMI_REQUIRE(workspace_bytes >= armi_sparse_rowlist_workspace_bytes(n_queries, k, max_list_rows),
+               "armi_sparse_rowlist_topk: workspace too small");
+  const int chunks = rowlist_chunks(max_list_rows);
+  const int direct = chunks == 1;
+  armi::Carver cv(workspace);
+  double* part_key = cv.take<double>(direct ? 0 : (size_t)n_queries * chunks * k);
+  int64_t* part_ord = cv.take<int64_t>(direct ? 0 : (size_t)n_queries * chunks * k);
+  sparse_rowlist_chunk_kernel<<<dim3(chunks, n_queries), dim3(kRlThreads), 0, stream>>>(
+      indptr, indices, values, n_rows, ordinal_base, q_indptr, q_indices, q_values, k, list_ptr,
+      list_rows, q_list, n_lists, max_list_rows, direct, part_key, part_ord, out_scores, out_ids,
+      out_count, out_flags);
+  ARMI_LAUNCHED("sparse_rowlist_chunk_kernel");
+  if (direct) return ARMI_OK;
+  sparse_rowlist_merge_kernel<<<dim3(n_queries), dim3(kRlThreads), 0, stream>>>(
+      part_key, part_ord, chunks, k, list_ptr, q_list, n_lists, max_list_rows, out_scores, out_ids,
+      out_count, out_flags);
+  ARMI_LAUNCHED("sparse_rowlist_merge_kernel");
+  return ARMI_OK;
+}
 
 int armi_sparse_index_create(int device, const int64_t* indptr, const int32_t* indices,
                              const float* values, int64_t n_rows, int64_t nnz, int32_t vocab,

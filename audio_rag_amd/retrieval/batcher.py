@@ -8,8 +8,10 @@ layer (BASELINE config 5 "streaming query at fixed QPS"
 submit single queries from any thread and get a Future of the reference-shaped
 list[RetrievalResult]; one worker thread drains the queue into batches of up to max_batch
 queries, waiting at most max_wait_ms after the first arrival, and runs one
-MI355XRetriever.search_batch per (filter, has-sparse) group. Per-query semantics are those of
-MI355XRetriever.search (qdrant.py:227-352); only the grouping is new.
+MI355XRetriever.search_batch per (filter, has-sparse) group; with the retriever's
+filter_list_rows knob on, one per has-sparse group, the requests' filters going along as
+search_batch's per-query list. Per-query semantics are those of MI355XRetriever.search
+(qdrant.py:227-352); only the grouping is new.
 """
 
 from __future__ import annotations
@@ -27,7 +29,8 @@ import torch
 
 from audio_rag_amd.core.base import EmbeddingResult, RetrievalResult
 from audio_rag_amd.core.exceptions import RetrievalError
-from audio_rag_amd.retrieval.mi355x import MI355XRetriever, QueryBatch, query_sparse_arrays
+from audio_rag_amd.retrieval.mi355x import (MI355XRetriever, QueryBatch, filter_key,
+                                            query_sparse_arrays)
 
 logger = logging.getLogger(__name__)
 
@@ -41,8 +44,7 @@ class _Request:
     t_submit: float = field(default_factory=time.perf_counter)
 
 
-def _filter_key(f: dict | None):
-    return None if not f else tuple(sorted((k, repr(v)) for k, v in f.items()))
+_filter_key = filter_key
 
 
 def _sorted_terms(indices, values) -> tuple[np.ndarray, np.ndarray]:
@@ -155,9 +157,14 @@ class QueryBatcher:
             if first is None:
                 break
             batch, stop = self._collect(first)
+            # with the retriever's filter_list_rows knob on, a batch keeps its queries' own
+            # filters (search_batch's list form: its planner groups them); off, one search per
+            # filter as before
+            mixed = self._mixed_filters()
             groups: dict = {}
             for r in batch:
-                groups.setdefault((_filter_key(r.filter_metadata), r.sparse is not None), []).append(r)
+                fk = None if mixed else _filter_key(r.filter_metadata)
+                groups.setdefault((fk, r.sparse is not None), []).append(r)
             for reqs in groups.values():
                 self._serve(reqs)
             if stop:
@@ -170,6 +177,10 @@ class QueryBatcher:
                 break
             if item is not None and not item.future.done():
                 item.future.set_exception(RetrievalError("QueryBatcher closed"))
+
+    def _mixed_filters(self) -> bool:
+        r = self.retriever
+        return r.config.filter_list_rows > 0 and r._world == 1
 
     def _serve(self, reqs: list[_Request]) -> None:
         try:
@@ -186,8 +197,9 @@ class QueryBatcher:
                 qb = QueryBatch(dense=dense, sparse_indptr=t(indptr), sparse_indices=t(idx),
                                 sparse_values=t(val))
             resolved = r._resolve_collection(self.collection_name)
-            out, mode = r.search_batch(qb, self.top_k, resolved, reqs[0].filter_metadata,
-                                       self.search_type)
+            filt = ([q.filter_metadata for q in reqs] if self._mixed_filters()
+                    else reqs[0].filter_metadata)
+            out, mode = r.search_batch(qb, self.top_k, resolved, filt, self.search_type)
             thr = None
             if mode == "legacy_dense" and r.config.score_threshold > 0:
                 thr = r.config.score_threshold

@@ -117,6 +117,7 @@ class ChunkCollection:
     _main_rows: int = 0      # points held by the main indexes
     _vmax: int = -1          # largest sparse term id upserted so far
     _seg_mask_cache: dict = field(default_factory=dict)
+    _seg_rows_cache: dict = field(default_factory=dict)   # filter key -> segment_row_lists
 
     def shard_bounds(self, n: int | None = None) -> tuple[int, int]:
         """[lo, hi) ordinals of this rank's shard of n (default: every) points."""
@@ -149,6 +150,7 @@ class ChunkCollection:
             self.payloads.extend(payloads)
             self._mask_cache.clear()
             self._seg_mask_cache.clear()
+            self._seg_rows_cache.clear()
             self._key_index.clear()
             self._vmax = max([self._vmax] + [int(s[0].max(initial=-1)) for s in sparse
                                              if s is not None])
@@ -248,6 +250,7 @@ class ChunkCollection:
                                        max(BGE_M3_VOCAB, self._vmax + 1), ordinal_base=0)
         self._main_rows = int(rows.shape[0])
         self._seg_mask_cache.clear()
+        self._seg_rows_cache.clear()
         del old
 
     def _flush_live(self) -> None:
@@ -329,6 +332,39 @@ class ChunkCollection:
         self._seg_mask_cache[key] = ((n, seg.main_rows), masks)
         return masks
 
+    def segment_row_lists(self, filter_metadata: dict, max_rows: int | None = None):
+        """filter_rows per segment, for the row-list searches (DenseIndex.topk_rows):
+        (main rows, tail rows, matches), the first two int32 device tensors of ascending local rows
+        (main: ordinal - the main indexes' ordinal base; tail: ordinal - main_rows, None without a
+        tail), matches their total over this rank's rows. A filter matching more than max_rows rows
+        is only counted (both lists None: its search will be a masked scan). Cached per filter
+        like segment_masks, and dropped with it (an upsert, a fold, a compaction)."""
+        seg = self.segments()
+        live = seg.tail is not None and seg.tail.n_rows > 0
+        key = tuple(sorted((k, repr(v)) for k, v in filter_metadata.items()))
+        state = (self.count, seg.main_rows, live)
+        cached = self._seg_rows_cache.get(key)
+        if cached is not None and cached[0] == state and (
+                cached[1][0] is not None or (max_rows is not None and cached[1][2] > max_rows)):
+            return cached[1]
+        rows = self.filter_rows(filter_metadata)
+        if not live:
+            lo, hi = self.shard_bounds(self.count)
+            rows = rows[np.searchsorted(rows, lo):np.searchsorted(rows, hi)]
+        if max_rows is not None and len(rows) > max_rows:
+            lists = (None, None, len(rows))
+            self._seg_rows_cache[key] = (state, lists)
+            return lists
+        if live:
+            cut = int(np.searchsorted(rows, seg.main_rows))
+            parts = (rows[:cut], rows[cut:] - seg.main_rows)
+        else:
+            parts = (rows - lo, None)
+        up = lambda a: None if a is None else torch.from_numpy(a.astype(np.int32)).to(self.device)
+        lists = (up(parts[0]), up(parts[1]), sum(len(a) for a in parts if a is not None))
+        self._seg_rows_cache[key] = (state, lists)
+        return lists
+
     def query_graphs(self) -> dict:
         """The captured single-query searches of the current indexes (key -> graph)."""
         self._ensure_built()
@@ -371,10 +407,40 @@ class ChunkCollection:
         self._mask_cache[key] = (n, mask)
         return mask
 
-    def _key_matches(self, key: str, wanted, n: int) -> np.ndarray:
-        """bool [n]: points whose metadata[key] matches `wanted` (_match_value). One pass over
-        the payloads per metadata key (cached until the next upsert) builds an inverted map
-        value-class -> ordinals, so a new filter value costs O(matches), not O(points)."""
+    def filter_rows(self, filter_metadata: dict | None) -> np.ndarray:
+        """Ascending unique int64 ordinals of the points whose payload metadata matches every
+        condition (the set filter_mask marks; every point without a filter). A condition whose
+        wanted value is a canonical scalar and whose key holds no value of an unusual type takes
+        the key index's ordinal arrays directly, and those are intersected: O(matches), not
+        O(points). Any other condition goes through _key_matches."""
+        n = self.count
+        if not filter_metadata:
+            return np.arange(n, dtype=np.int64)
+        rows = None
+        general = []
+        for k, v in filter_metadata.items():
+            c = _canon(v)
+            if c is None:
+                general.append((k, v))
+                continue
+            _, inv, gen = self._key_entry(k, n)
+            if gen:
+                general.append((k, v))
+                continue
+            hit = inv.get(c) if c is not _NO_MATCH else None
+            if hit is None:
+                return np.zeros(0, dtype=np.int64)
+            rows = hit if rows is None else np.intersect1d(rows, hit, assume_unique=True)
+        if general:
+            ok = np.ones(n, dtype=bool)
+            for k, v in general:
+                ok &= self._key_matches(k, v, n)
+            rows = np.nonzero(ok)[0] if rows is None else rows[ok[rows]]
+        return np.ascontiguousarray(rows, dtype=np.int64)
+
+    def _key_entry(self, key: str, n: int) -> tuple:
+        """The key index of a metadata key over the first n points: (n, {value class: ascending
+        unique ordinals}, points whose value needs the general comparison)."""
         cached = self._key_index.get(key)
         if cached is None or cached[0] != n:
             inv: dict = {}
@@ -393,7 +459,13 @@ class ChunkCollection:
             cached = (n, {c: np.unique(np.asarray(v, dtype=np.int64)) for c, v in inv.items()},
                       general)
             self._key_index[key] = cached
-        _, inv, general = cached
+        return cached
+
+    def _key_matches(self, key: str, wanted, n: int) -> np.ndarray:
+        """bool [n]: points whose metadata[key] matches `wanted` (_match_value). One pass over
+        the payloads per metadata key (cached until the next upsert) builds an inverted map
+        value-class -> ordinals, so a new filter value costs O(matches), not O(points)."""
+        _, inv, general = self._key_entry(key, n)
         ok = np.zeros(n, dtype=bool)
         c = _canon(wanted)
         if c is not None and c is not _NO_MATCH and c in inv:

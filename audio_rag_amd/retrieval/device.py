@@ -61,6 +61,36 @@ class TopK:
                      if t is not None)
 
 
+def _check_row_lists(list_ptr: torch.Tensor, list_rows: torch.Tensor, q_list: torch.Tensor,
+                     n_queries: int, max_list_rows: int, n_rows: int,
+                     device: torch.device) -> int:
+    """Argument checks of the row-list encoding shared by DenseIndex.topk_rows and
+    SparseIndex.topk_rows (include/armi.h, armi_dense_rowlist_topk); returns n_lists. q_list is
+    checked for its range only when it lives on the host (a device q_list is not read back: that
+    would synchronise every call)."""
+    for t, dt, name in ((list_ptr, torch.int64, "list_ptr"), (list_rows, torch.int32, "list_rows"),
+                        (q_list, torch.int32, "q_list")):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 1:
+            raise ValueError(f"{name} must be a 1-D {dt} tensor")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    n_lists = int(list_ptr.numel()) - 1
+    if n_lists < 1:
+        raise ValueError("list_ptr must hold at least one list (n_lists + 1 offsets)")
+    if int(q_list.numel()) != n_queries:
+        raise ValueError(f"q_list names {q_list.numel()} lists for {n_queries} queries")
+    if not q_list.is_cuda and n_queries and not (0 <= int(q_list.min()) and
+                                                 int(q_list.max()) < n_lists):
+        raise ValueError(f"q_list entries must be in [0, {n_lists})")
+    if not 0 <= max_list_rows <= n_rows:
+        raise ValueError(f"max_list_rows must be in [0, {n_rows}]")
+    return n_lists
+
+
+def _on_device(t: torch.Tensor, device: torch.device) -> torch.Tensor:
+    return t if t.is_cuda else t.to(device)
+
+
 def _check_fp16_2d(t: torch.Tensor, name: str, dim: int | None = None) -> None:
     if not isinstance(t, torch.Tensor) or t.dtype != torch.float16 or t.dim() != 2:
         raise ValueError(f"{name} must be a 2-D float16 tensor")
@@ -169,6 +199,44 @@ class DenseIndex:
             call("armi_dense_topk", self._handle, ptr(queries), b, k, ptr(row_mask),
                  ptr(out.scores), ptr(out.ids), ptr(out.rank), ptr(out.count), ptr(out.flags),
                  ptr(workspace), workspace.numel(), s)
+        return out
+
+    def rowlist_workspace_bytes(self, n_queries: int, k: int, max_list_rows: int) -> int:
+        return int(query("armi_dense_rowlist_workspace_bytes", self._handle, n_queries, k,
+                         int(max_list_rows)))
+
+    def topk_rows(self, queries: torch.Tensor, k: int, list_ptr: torch.Tensor,
+                  list_rows: torch.Tensor, q_list: torch.Tensor, max_list_rows: int,
+                  workspace: torch.Tensor | None = None, out: TopK | None = None) -> TopK:
+        """Cosine top-k of every query over the rows of its list instead of a masked scan
+        (armi_dense_rowlist_topk): list l = list_rows[list_ptr[l] : list_ptr[l + 1]], ascending
+        unique int32 local rows; q_list int32 [B] names each query's list; max_list_rows >= the
+        longest list (a host value: it sizes the grid). list_ptr / q_list may be host tensors
+        (they are uploaded); the same ranking, scores and rank keys as topk(row_mask=...), flags
+        ARMI_FLAG_ROWLIST."""
+        _check_fp16_2d(queries, "queries", self.dim)
+        if not 1 <= k <= MAX_K:
+            raise ValueError(f"k must be in [1, {MAX_K}]")
+        b = int(queries.shape[0])
+        dev = self.device
+        n_lists = _check_row_lists(list_ptr, list_rows, q_list, b, int(max_list_rows),
+                                   self.n_rows, dev)
+        list_ptr, list_rows, q_list = (_on_device(t, dev) for t in (list_ptr, list_rows, q_list))
+        if out is None:
+            out = TopK(scores=torch.empty((b, k), dtype=torch.float32, device=dev),
+                       ids=torch.empty((b, k), dtype=torch.int64, device=dev),
+                       rank=torch.empty((b, k), dtype=torch.float64, device=dev),
+                       count=torch.empty(b, dtype=torch.int32, device=dev),
+                       flags=torch.empty(b, dtype=torch.int32, device=dev))
+        if b == 0:
+            return out
+        need = self.rowlist_workspace_bytes(b, k, max_list_rows)
+        if workspace is None or workspace.numel() < need:
+            workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        call("armi_dense_rowlist_topk", self._handle, ptr(queries), b, k, ptr(list_ptr),
+             ptr(list_rows), ptr(q_list), n_lists, int(max_list_rows), ptr(out.scores),
+             ptr(out.ids), ptr(out.rank), ptr(out.count), ptr(out.flags), ptr(workspace),
+             workspace.numel(), stream_handle())
         return out
 
 
@@ -314,6 +382,44 @@ class SparseIndex:
         call("armi_sparse_topk", self._handle, ptr(q_indptr), ptr(q_indices), ptr(q_values), b, k,
              ptr(row_mask), ptr(out.scores), ptr(out.ids), ptr(out.count), ptr(out.flags),
              ptr(workspace), workspace.numel(), stream_handle())
+        return out
+
+    @staticmethod
+    def rowlist_workspace_bytes(n_queries: int, k: int, max_list_rows: int) -> int:
+        return int(query("armi_sparse_rowlist_workspace_bytes", n_queries, k, int(max_list_rows)))
+
+    def topk_rows(self, q_indptr: torch.Tensor, q_indices: torch.Tensor, q_values: torch.Tensor,
+                  k: int, list_ptr: torch.Tensor, list_rows: torch.Tensor, q_list: torch.Tensor,
+                  max_list_rows: int, workspace: torch.Tensor | None = None) -> TopK:
+        """Sparse dot top-k of every query over the rows of its list, from this index's forward
+        CSR (armi_sparse_rowlist_topk; the list arguments as DenseIndex.topk_rows): the same
+        ranking and scores as topk(row_mask=...), flags ARMI_FLAG_ROWLIST."""
+        if not 1 <= k <= MAX_K:
+            raise ValueError(f"k must be in [1, {MAX_K}]")
+        for t, dt, name in ((q_indptr, torch.int32, "q_indptr"), (q_indices, torch.int32, "q_indices"),
+                            (q_values, torch.float32, "q_values")):
+            if t.dtype != dt or t.dim() != 1 or not t.is_cuda or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous 1-D {dt} device tensor")
+        b = int(q_indptr.numel()) - 1
+        dev = self.device
+        n_lists = _check_row_lists(list_ptr, list_rows, q_list, max(b, 0), int(max_list_rows),
+                                   self.n_rows, dev)
+        list_ptr, list_rows, q_list = (_on_device(t, dev) for t in (list_ptr, list_rows, q_list))
+        out = TopK(scores=torch.empty((max(b, 0), k), dtype=torch.float32, device=dev),
+                   ids=torch.empty((max(b, 0), k), dtype=torch.int64, device=dev),
+                   count=torch.empty(max(b, 0), dtype=torch.int32, device=dev),
+                   flags=torch.empty(max(b, 0), dtype=torch.int32, device=dev))
+        if b <= 0:
+            return out
+        need = self.rowlist_workspace_bytes(b, k, max_list_rows)
+        if workspace is None or workspace.numel() < need:
+            workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            call("armi_sparse_rowlist_topk", ptr(self.indptr), ptr(self.indices), ptr(self.values),
+                 self.n_rows, self.ordinal_base, ptr(q_indptr), ptr(q_indices), ptr(q_values), b, k,
+                 ptr(list_ptr), ptr(list_rows), ptr(q_list), n_lists, int(max_list_rows),
+                 ptr(out.scores), ptr(out.ids), ptr(out.count), ptr(out.flags), ptr(workspace),
+                 workspace.numel(), stream_handle())
         return out
 
 

@@ -74,6 +74,45 @@ def query_sparse_arrays(sv: SparseVector | None) -> tuple[np.ndarray, np.ndarray
     return arr
 
 
+def filter_key(f: dict | None):
+    """The identity of a metadata filter (None for no filter): queries with equal keys share one
+    search."""
+    return None if not f else tuple(sorted((k, repr(v)) for k, v in f.items()))
+
+
+@dataclass
+class FilterGroup:
+    """The queries of one search_batch call that carry one filter, and the planner's choice."""
+
+    filter: dict | None
+    queries: list
+    matches: int = -1       # rows the filter matches (-1: not counted, the knob is off / no filter)
+    rowlist: bool = False   # ranked from the matching rows (armi_*_rowlist_topk), else a masked scan
+
+
+def plan_filter_groups(filters: list, n_rows: int, knob: int, count_matches) -> list[FilterGroup]:
+    """Groups the queries of a batch by filter (in order of first appearance) and picks each
+    group's path. A group of q queries whose filter matches m of the collection's n_rows rows is
+    ranked from its row list iff the knob is on (filter_list_rows > 0), m <= knob and
+    2 * q * m <= n_rows: byte parity, the list path reads at most 2 B per component, row and
+    query (fp16 rows, once per query), the masked scan at least 1 B per component and row (the
+    int8 image, once per pass of up to 64 queries), so a chosen list never reads more than the scan
+    it replaces. An empty match list always qualifies (count 0). Queries without a filter, and
+    every group the rule refuses, take the masked scan. count_matches(filter) -> m is asked only
+    with the knob on. For a live collection m and n_rows count both segments."""
+    groups: dict = {}
+    for i, f in enumerate(filters):
+        g = groups.get(filter_key(f))
+        if g is None:
+            g = groups[filter_key(f)] = FilterGroup(f or None, [])
+        g.queries.append(i)
+    for g in groups.values():
+        if knob > 0 and g.filter:
+            g.matches = int(count_matches(g.filter))
+            g.rowlist = g.matches <= knob and 2 * len(g.queries) * g.matches <= n_rows
+    return list(groups.values())
+
+
 def fp16_rows(vectors: list[list[float]] | np.ndarray, dim: int) -> np.ndarray:
     a = np.asarray(vectors, dtype=np.float32)
     if a.ndim != 2 or a.shape[1] != dim:
@@ -166,6 +205,8 @@ class MI355XRetriever(BaseRetriever):
         self._hybrid: ConcurrentHybrid | None = None
         self._graphs_ok = True  # cleared when a capture is refused (search() then runs eagerly)
         self.last_sharded = None  # the ShardedSearch of the last collective call (diagnostics)
+        self.last_plan: list[FilterGroup] | None = None  # the last planned call's groups (same)
+        self._enc_cache: dict = {}  # (filter, queries) -> (row lists, their encoding): one group
         # num_gpus > 1: the corpus is sharded by ordinal over the ranks of the default process
         # group (one process per GPU, launched by torchrun, torch.distributed initialised and
         # the process's GPU selected before the retriever is built): see _search_sharded
@@ -322,20 +363,188 @@ class MI355XRetriever(BaseRetriever):
         return "dense" if coll.hybrid else "legacy_dense"
 
     def search_batch(self, queries: QueryBatch, top_k: int | None = None,
-                     collection_name: str | None = None, filter_metadata: dict | None = None,
+                     collection_name: str | None = None,
+                     filter_metadata: dict | list | None = None,
                      search_type: str | None = None) -> tuple[TopK, str]:
         """Device top-k for B queries; returns (TopK, mode). Scores are cosine (dense),
-        sparse dot (sparse) or the RRF score (hybrid), as Qdrant's hit.score."""
+        sparse dot (sparse) or the RRF score (hybrid), as Qdrant's hit.score. filter_metadata: one
+        filter for every query, or a list of one `dict | None` per query (the reference's API
+        takes one filter per request, api/v1/query.py:41). With config.filter_list_rows > 0 the
+        queries are grouped by filter and selective groups are ranked from their matching rows
+        (plan_filter_groups); the answers do not depend on the path, only TopK.flags tell
+        (ARMI_FLAG_ROWLIST). With num_gpus > 1 the knob is ignored and the list form refused."""
         resolved = self._ensure_collection(collection_name)
         top_k = top_k or self.config.top_k
         search_type = search_type or self.config.search_type
         coll = self._collections[resolved]
         mode = self._mode(coll, search_type, queries.has_sparse)
+        per_query = isinstance(filter_metadata, (list, tuple))
         if self._world > 1:
+            if per_query:
+                raise RetrievalError("one filter per query needs num_gpus = 1: the collective "
+                                     "search of a sharded corpus agrees on one filter per call")
             mask = coll.filter_mask(filter_metadata)
             return self._search_sharded(coll, queries, top_k, mode, mask, filter_metadata), mode
-        return self._search_device(coll, queries, top_k, mode,
-                                   coll.segment_masks(filter_metadata)), mode
+        b = int(queries.dense.shape[0])
+        if per_query and len(filter_metadata) != b:
+            raise RetrievalError(f"{len(filter_metadata)} filters for {b} queries")
+        if not per_query and (self.config.filter_list_rows == 0 or not filter_metadata):
+            return self._search_device(coll, queries, top_k, mode,
+                                       coll.segment_masks(filter_metadata)), mode
+        filters = list(filter_metadata) if per_query else [filter_metadata] * b
+        return self._search_planned(coll, queries, top_k, mode, filters), mode
+
+    def _search_planned(self, coll: ChunkCollection, queries: QueryBatch, top_k: int, mode: str,
+                        filters: list) -> TopK:
+        """search_batch with one filter per query: the planner's groups (plan_filter_groups), all
+        row-list groups in one dense and one sparse launch per segment, every other group by
+        today's masked search, one call per group; the results scattered back in query order with
+        their flags (ARMI_FLAG_ROWLIST on the row-list queries)."""
+        from audio_rag_amd._armi import ARMI_FLAG_ROWLIST
+
+        seg = coll.segments()
+        b = int(queries.dense.shape[0])
+        knob = self.config.filter_list_rows
+        n_rows = seg.dense.n_rows + (seg.tail.n_rows if seg.tail is not None else 0)
+        groups = plan_filter_groups(filters, n_rows, knob,
+                                    lambda f: coll.segment_row_lists(f, knob)[2])
+        self.last_plan = groups
+        if len(groups) == 1 and not groups[0].rowlist:  # one masked search, as without a plan
+            return self._search_device(coll, queries, top_k, mode,
+                                       coll.segment_masks(groups[0].filter))
+        parts = []  # (query indexes, their TopK, flag bits to add)
+        listed = [g for g in groups if g.rowlist]
+        if listed:
+            idx = [i for g in listed for i in g.queries]
+            out = self._search_rowlists(seg, self._select(queries, idx), top_k, mode,
+                                        *self._encode_rowlists(coll, listed))
+            parts.append((idx, out, ARMI_FLAG_ROWLIST))
+        for g in groups:
+            if not g.rowlist:
+                out = self._search_device(coll, self._select(queries, g.queries), top_k, mode,
+                                          coll.segment_masks(g.filter))
+                parts.append((g.queries, out, 0))
+        return self._scatter(parts, b)
+
+    def _select(self, queries: QueryBatch, idx: list) -> QueryBatch:
+        """The queries idx of a batch as a batch of their own, built on the device without reading
+        anything back: the term arrays keep the whole batch's length (an upper bound), filled up to
+        the new indptr's end."""
+        if idx == list(range(int(queries.dense.shape[0]))):
+            return queries
+        dev = queries.dense.device
+        it = torch.tensor(idx, dtype=torch.int64, device=dev)
+        dense = queries.dense.index_select(0, it)
+        if not queries.has_sparse:
+            return QueryBatch(dense=dense)
+        ptr = queries.sparse_indptr.to(torch.int64)
+        starts = ptr[:-1][it]
+        new_ptr = torch.zeros(len(idx) + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(ptr[1:][it] - starts, 0, out=new_ptr[1:])
+        cap = int(queries.sparse_indices.numel())
+        indices, values = queries.sparse_indices, queries.sparse_values
+        if cap and idx:
+            pos = torch.arange(cap, dtype=torch.int64, device=dev)
+            j = (torch.searchsorted(new_ptr, pos, right=True) - 1).clamp_(0, len(idx) - 1)
+            src = (starts[j] + (pos - new_ptr[j])).clamp_(0, cap - 1)
+            indices, values = indices[src], values[src]
+        return QueryBatch(dense=dense, sparse_indptr=new_ptr.to(torch.int32),
+                          sparse_indices=indices, sparse_values=values)
+
+    def _encode_rowlists(self, coll: ChunkCollection, groups: list[FilterGroup]):
+        """The row lists of the groups' filters in the kernels' encoding, per segment: (main, tail),
+        each (list_ptr, list_rows, q_list, longest list) on the device with one list per group and
+        the queries in the groups' order; tail None when the collection has no tail rows."""
+        dev = self.device
+        lists = [coll.segment_row_lists(g.filter, self.config.filter_list_rows) for g in groups]
+        # one group (search(), a batch under one filter): the encoding is kept with the lists it
+        # was made from, so a repeated filter uploads nothing
+        one = (self._enc_cache.get((filter_key(groups[0].filter), len(groups[0].queries)))
+               if len(groups) == 1 else None)
+        if one is not None and one[0] is lists[0]:
+            return one[1]
+        q_list = torch.from_numpy(np.repeat(np.arange(len(groups), dtype=np.int32),
+                                            [len(g.queries) for g in groups])).to(dev)
+
+        def encode(which: int):
+            rows = [ls[which] for ls in lists]
+            if any(r is None for r in rows):
+                return None
+            ptr = np.zeros(len(rows) + 1, dtype=np.int64)
+            np.cumsum([r.numel() for r in rows], out=ptr[1:])
+            return (torch.from_numpy(ptr).to(dev), torch.cat(rows), q_list,
+                    max(r.numel() for r in rows))
+
+        enc = encode(0), encode(1)
+        if len(groups) == 1:
+            if len(self._enc_cache) >= 1024:
+                self._enc_cache.clear()
+            key = (filter_key(groups[0].filter), len(groups[0].queries))
+            self._enc_cache[key] = (lists[0], enc)
+        return enc
+
+    def _search_rowlists(self, seg, queries: QueryBatch, top_k: int, mode: str, main: tuple,
+                         tail: tuple | None) -> TopK:
+        """The row-list groups of a planned call (_encode_rowlists' lists, the queries in the same
+        order): one dense and one sparse launch per segment, the segments' lists merged exactly
+        (merge_shards, as _search_device merges the sparse segments), hybrid through the same RRF.
+        Device work only (graph-capturable)."""
+        from audio_rag_amd.retrieval.device import merge_shards
+
+        live = tail is not None and tail[3] > 0  # no tail match: the main lists are the answer
+        sq = (queries.sparse_indptr, queries.sparse_indices, queries.sparse_values)
+
+        def merged(a: TopK, t: TopK, k: int) -> TopK:
+            m = merge_shards(torch.stack([a.rank, t.rank]), torch.stack([a.scores, t.scores]),
+                             torch.stack([a.ids, t.ids]), torch.stack([a.count, t.count]), k)
+            m.flags = a.flags
+            return m
+
+        def dense(k: int) -> TopK:
+            d = seg.dense.topk_rows(queries.dense, k, *main)
+            return merged(d, seg.tail.topk_rows(queries.dense, k, *tail), k) if live else d
+
+        def sparse(k: int) -> TopK:
+            s = seg.sparse.topk_rows(*sq, k, *main)
+            return merged(s, seg.tail_sparse.topk_rows(*sq, k, *tail), k) if live else s
+
+        if mode == "hybrid":
+            if self._hybrid is None:
+                self._hybrid = ConcurrentHybrid(self.device)
+            extra = main[:3] + (tail[:3] if live else ())
+            return self._hybrid(lambda: dense(2 * top_k), lambda: sparse(2 * top_k), sq + extra,
+                                top_k, rrf_k=self.config.rrf_k)
+        if mode == "sparse":
+            return sparse(top_k)
+        return dense(top_k)
+
+    def _scatter(self, parts: list, b: int) -> TopK:
+        """One TopK in query order from the groups' results: parts = (query indexes, TopK, flag
+        bits the group adds). Only the tensors every part holds are copied (the others convert on
+        access, TopK); flags are always present."""
+        dev = self.device
+        if len(parts) == 1 and parts[0][0] == list(range(b)):  # one group: nothing to reorder
+            _, out, bits = parts[0]
+            if out.flags is None:
+                out.flags = torch.full((b,), bits, dtype=torch.int32, device=dev)
+            elif bits:
+                out.flags |= bits
+            return out
+        names = [n for n in ("_scores", "ids", "_rank", "count")
+                 if all(getattr(p, n) is not None for _, p, _ in parts)]
+        first = parts[0][1]
+        out = TopK(flags=torch.zeros(b, dtype=torch.int32, device=dev))
+        for n in names:
+            t = getattr(first, n)
+            setattr(out, n, torch.empty((b,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev))
+        for idx, p, bits in parts:
+            it = torch.tensor(idx, dtype=torch.int64, device=dev)
+            for n in names:
+                getattr(out, n).index_copy_(0, it, getattr(p, n))
+            flags = p.flags | bits if p.flags is not None else torch.full(
+                (len(idx),), bits, dtype=torch.int32, device=dev)
+            out.flags.index_copy_(0, it, flags.to(torch.int32))
+        return out
 
     def _search_sharded(self, coll: ChunkCollection, queries: QueryBatch, top_k: int, mode: str,
                         mask: torch.Tensor | None, mask_spec: dict | None = None) -> TopK:

@@ -56,14 +56,18 @@ extern "C" {
  * transposed ([in][out], was [out][in]); armi_dense_topk_ex / _first / _second_pass,
  * armi_index_set_scan_cus and armi_cu_split_streams removed. A caller built against version 1
  * must not bind this library (armi_abi_version() tells). 3: growable fp16 segments
- * (armi_index_create_tail / _append / _capacity) and armi_dense_tail_topk; nothing removed. */
-#define ARMI_ABI_VERSION 3
+ * (armi_index_create_tail / _append / _capacity) and armi_dense_tail_topk; nothing removed.
+ * 4: row-list top-k (armi_dense_rowlist_topk, armi_sparse_rowlist_topk, ARMI_FLAG_ROWLIST);
+ * nothing removed. */
+#define ARMI_ABI_VERSION 4
 
 /* flags written per query by the top-k entry points */
 #define ARMI_FLAG_CERTIFIED 1u /* fast path proved its top-k equal to the exact ranking */
 #define ARMI_FLAG_FALLBACK 2u  /* fast path could not prove it; exact scan produced the answer */
 #define ARMI_FLAG_FILTERED 4u  /* sparse: answered by the MFMA filter + exact rescore (with
                                 * ARMI_FLAG_CERTIFIED) instead of the exact scan */
+#define ARMI_FLAG_ROWLIST 8u   /* answered by a row-list entry point (armi_*_rowlist_topk): the exact
+                                * ranking of the listed rows by construction, no certificate */
 
 const char* armi_last_error(void);
 int armi_abi_version(void);
@@ -188,6 +192,34 @@ int armi_dense_tail_topk(const armi_index* tail, const uint16_t* queries, int n_
                          const int32_t* main_count, float* out_scores, int64_t* out_ids,
                          double* out_rank, int32_t* out_count, uint32_t* out_flags,
                          void* workspace, size_t workspace_bytes, hipStream_t stream);
+
+/* Cosine top-k over given rows of the index instead of a masked scan of all of it: the search of
+ * a selective metadata filter (Qdrant scores the matching points directly when a payload filter's
+ * cardinality is low; src/audio_rag/retrieval/qdrant.py:263-269 builds that filter). The rows are
+ * n_lists row lists in one encoding, shared with armi_sparse_rowlist_topk:
+ *   list_ptr       int64 [n_lists + 1]; list l is list_rows[list_ptr[l] .. list_ptr[l + 1])
+ *   list_rows      int32 local rows of the index, ascending and unique within a list, each in
+ *                  [0, rows of the index) (an entry outside that range is skipped)
+ *   q_list         int32 [n_queries]: the list query q is ranked over, in [0, n_lists); several
+ *                  queries may share a list and a list may be unused
+ *   max_list_rows  host value >= the longest list's length (<= rows of the index); it sizes the
+ *                  grid and the workspace, and rows of a list past it are not ranked
+ * Outputs and ranking as armi_dense_topk (key = (double)dot64 * inv_norm[row], (key desc, ordinal
+ * asc), score (float)(key / |q|), -1 / -inf past out_count, out_rank nullable); out_count < k when
+ * the list holds fewer valid rows. Rows outside the fp16 domain (norm2 < 0) are skipped as every
+ * scan skips them. Every query gets ARMI_FLAG_ROWLIST: the keys are exact, so there is no
+ * certificate and no fallback. Reads only the fp16 rows and the norm arrays, so a growable tail
+ * index (no int8 image) is searched the same way. One workgroup scores 512 rows of one query's
+ * list exactly and keeps their top k; lists longer than that add one merge workgroup per query.
+ * No host synchronisation; graph-capture safe. k 1..240, n_queries <= 65535. */
+size_t armi_dense_rowlist_workspace_bytes(const armi_index* index, int n_queries, int k,
+                                          int64_t max_list_rows);
+int armi_dense_rowlist_topk(const armi_index* index, const uint16_t* queries, int n_queries, int k,
+                            const int64_t* list_ptr, const int32_t* list_rows,
+                            const int32_t* q_list, int n_lists, int64_t max_list_rows,
+                            float* out_scores, int64_t* out_ids, double* out_rank,
+                            int32_t* out_count, uint32_t* out_flags, void* workspace,
+                            size_t workspace_bytes, hipStream_t stream);
 
 size_t armi_dense_exact_workspace_bytes(const armi_index* index, int n_queries, int k);
 /* Exhaustive exact scan with the same outputs and ranking as armi_dense_topk. */
@@ -346,6 +378,27 @@ int armi_sparse_topk(const armi_sparse_index* index, const int32_t* q_indptr,
                      const uint64_t* row_mask, float* out_scores, int64_t* out_ids,
                      int32_t* out_count, uint32_t* out_flags, void* workspace,
                      size_t workspace_bytes, hipStream_t stream);
+
+/* Sparse dot-product top-k over given rows (armi_dense_rowlist_topk's list encoding: list_ptr,
+ * list_rows, q_list, n_lists, max_list_rows), computed from the forward CSR the caller built the
+ * index from (indptr int64 [n_rows + 1], indices int32 ascending per row, values float: device
+ * memory on the current device), not from the inverted index. Query CSR as armi_sparse_topk, every
+ * term scored (no 256-term limit). score = the merge join of the row's and the query's ascending
+ * indices, fl32(q*d) per shared index added in fp32 in that order (mul and add rounded
+ * separately): armi_sparse_topk's exact score. A row is a result when it shares at least one index
+ * with the query, also when its score is 0 or negative; a query without terms gets count 0.
+ * Ranking (score desc, ordinal asc), ordinal = ordinal_base + row; -1 / -inf past out_count;
+ * every query gets ARMI_FLAG_ROWLIST. No host synchronisation; graph-capture safe. k 1..240,
+ * n_queries <= 65535. */
+size_t armi_sparse_rowlist_workspace_bytes(int n_queries, int k, int64_t max_list_rows);
+int armi_sparse_rowlist_topk(const int64_t* indptr, const int32_t* indices, const float* values,
+                             int64_t n_rows, int64_t ordinal_base, const int32_t* q_indptr,
+                             const int32_t* q_indices, const float* q_values, int n_queries, int k,
+                             const int64_t* list_ptr, const int32_t* list_rows,
+                             const int32_t* q_list, int n_lists, int64_t max_list_rows,
+                             float* out_scores, int64_t* out_ids, int32_t* out_count,
+                             uint32_t* out_flags, void* workspace, size_t workspace_bytes,
+                             hipStream_t stream);
 
 /* Enables (1) or disables (0) the MFMA filter of armi_sparse_topk on this index (default on:
  * the exact scan alone when off); usable (host, nullable) = 1 when the index can use the filter
