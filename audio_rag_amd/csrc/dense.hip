@@ -94,12 +94,17 @@ __device__ __forceinline__ f32x16 mfma16(u32x4 a, u32x4 b, f32x16 c) {
 // this access shape ran the scan at 3.3 TB/s instead of 5.4 TB/s.
 __device__ __forceinline__ u32x4 stream_load(const u32x4* p) { return *p; }
 
+// LDS bytes of the scans' workgroup merge scratch: lkey / lrow [kQB][65] (rows padded to 65 dwords)
+// and ldisc [kQB][17]. At dim 256 it is larger than the query image; sized without the padding it
+// left the discard bounds of the block's last queries past the allocation (reads of 0: a bound
+// that certified wrong lists).
+constexpr int kScanMergeScratch = kQB * 65 * 4 * 2 + kQB * 17 * 4;
+
 // LDS bytes of the scan kernel: the query fragment image, later overlaid by the merge scratch.
 template <int DIM>
 constexpr int scan_lds_bytes() {
   constexpr int img = (DIM / 16) * 2 * kQB * 16;
-  constexpr int scratch = kQB * 64 * 4 * 2 + kQB * 16 * 4;
-  return img > scratch ? img : scratch;
+  return img > kScanMergeScratch ? img : kScanMergeScratch;
 }
 
 // dense_scan_i8_kernel's query image (round 6): the 64 fp16 query rows as they are in memory,
@@ -111,8 +116,7 @@ constexpr int i8_qstride() { return DIM * 2 + 16; }
 template <int DIM>
 constexpr int i8_img_bytes() {
   constexpr int img = kQB * i8_qstride<DIM>();
-  constexpr int scratch = kQB * 64 * 4 * 2 + kQB * 16 * 4;
-  return img > scratch ? img : scratch;
+  return img > kScanMergeScratch ? img : kScanMergeScratch;
 }
 
 template <int DIM>
