@@ -25,7 +25,7 @@ ARMI_FLAG_FILTERED = 4
 ARMI_FLAG_ROWLIST = 8
 TIMING_DENSE_SCAN, TIMING_SPARSE_SCAN, TIMING_ENCODER_GEMM, TIMING_SPARSE_STAGE = 0, 1, 2, 3
 SCAN_FP16, SCAN_INT8_FILTER, SCAN_TILED_FP16, SCAN_TILED_INT8 = 0, 1, 2, 3  # armi_dense_scan_form
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 c_void_p = ctypes.c_void_p
 c_int = ctypes.c_int
@@ -57,6 +57,12 @@ SIGNATURES: dict[str, tuple] = {
                                          c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                          c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_size_t, c_void_p]),
+    "armi_sparse_tail_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "armi_sparse_tail_chunk_rows": (c_int, []),
+    "armi_sparse_tail_topk": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
+                                      c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_size_t, c_void_p]),
     "armi_dense_scan_form": (c_int, [c_void_p, c_int, c_int]),
     "armi_dense_scan_nontemporal": (c_int, [c_void_p, c_int, c_int]),
     "armi_index_destroy": (c_int, [c_void_p]),

@@ -2005,6 +2005,314 @@ int rowlist_chunks(int64_t max_list_rows) {
   return (int)std::max<int64_t>(1, (max_list_rows + kRlChunk - 1) / kRlChunk);
 }
 
+// ------------------------------------------------------------------------ sparse tail pass
+// armi_sparse_tail_topk: the exact scores of every row of a small forward CSR (the live tail),
+// merged into the main index's finished list. No inverted index, no certificate, no fallback.
+//
+// Scan, grid (chunks, queries): workgroup (c, q) scores tail rows [c * kStChunk, ...) for query q.
+// The query's first kMaxTerms (term, weight) pairs are staged in LDS in their ascending order,
+// padded to a power of two, and the chunk's indptr entries beside them. A wave owns a row: each
+// round its lanes read 2 x 64 consecutive postings (two coalesced index loads, two value loads),
+// every lane finds its term in the query table by a branch-free lower bound and the hitting lanes'
+// products fl32(w * v) are added into the wave's running sum in ascending lane order, the lower 64
+// postings before the upper 64, round after round. Postings are stored in ascending term order,
+// so the order of rounds, halves and lanes is the order of terms: the sum is the merge join's
+// (+0.0f, then one rounded multiply and one rounded add per shared term), bit for bit the exact
+// scan's and the oracle's. A wave issues the first round of kStBatch rows together, so
+// 4 * kStBatch loads are in flight per wave.
+//
+// A row is a result when it shares a term with the query and its mask bit is set. When the main
+// list is full, a result below the main k-th score cannot enter (a tie has a larger ordinal than
+// every main row; it is kept and the sort settles it), so only results >= that score survive;
+// when the main list is short every result survives. The chunk's survivors are compacted in row
+// order and cut to the chunk's best k when there are more: a chunk list cannot overflow. A tail
+// of one chunk is finished by the scan workgroup (`direct`: one launch); otherwise the chunk
+// lists go to the workspace (counts written, never accumulated) and sparse_tail_finish_kernel,
+// one workgroup per query, merges them with the main list.
+constexpr int kStChunk = 128;     // tail rows per scan workgroup
+constexpr int kStThreads = 256;
+constexpr int kStWaves = kStThreads / 64;
+constexpr int kStBatch = 4;       // rows whose first round a wave loads together
+constexpr int kStRowsPerWave = kStChunk / kStWaves;
+constexpr int kStSort = 512;      // direct finish: k main entries + a chunk's survivors
+constexpr int kStFinish = 1024;   // finish kernel: the best k + incoming chunk entries
+constexpr int kStGroup = 256;     // chunk counts scanned together by the finish kernel
+static_assert(kStRowsPerWave % kStBatch == 0, "whole batches per wave");
+static_assert(kStChunk + kMaxK <= kStSort && kStChunk <= kStThreads, "direct finish buffer");
+
+// Sorted key / ord [0, k) as query q's outputs (k <= blockDim.x); flags pass through.
+__device__ __forceinline__ void tail_write_out(const double* key, const int64_t* ord, int q, int k,
+                                               const uint32_t* __restrict__ main_flags,
+                                               float* __restrict__ out_scores,
+                                               int64_t* __restrict__ out_ids,
+                                               int32_t* __restrict__ out_count,
+                                               uint32_t* __restrict__ out_flags) {
+  const int tid = threadIdx.x;
+  const bool v = tid < k && ord[tid] != kRlNoOrd;
+  const int n_valid = __syncthreads_count(v);
+  if (tid < k) {
+    const size_t o = (size_t)q * k + tid;
+    out_scores[o] = v ? (float)key[tid] : kNegInf;
+    out_ids[o] = v ? ord[tid] : -1;
+  }
+  if (tid == 0) {
+    out_count[q] = n_valid;
+    if (out_flags) out_flags[q] = main_flags ? main_flags[q] : 0u;
+  }
+}
+
+// x, the same in every lane, as a scalar (loop bounds and branches on it stay scalar).
+__device__ __forceinline__ int64_t tail_uniform(int64_t x) {
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)x);
+  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)x >> 32));
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// The score a tail result of query q needs to survive: the k-th score of a full main list, -inf
+// while the main list is short.
+__device__ __forceinline__ float tail_threshold(const float* __restrict__ main_scores,
+                                                const int32_t* __restrict__ main_count, int q,
+                                                int k) {
+  const int mc = main_count[q];
+  return mc >= k ? main_scores[(size_t)q * k + k - 1] : kNegInf;
+}
+
+// The main list of query q into key / ord [0, k): its first min(main_count, k) entries, the rest
+// empty.
+__device__ __forceinline__ void tail_load_main(double* key, int64_t* ord,
+                                               const float* __restrict__ main_scores,
+                                               const int64_t* __restrict__ main_ids,
+                                               const int32_t* __restrict__ main_count, int q,
+                                               int k) {
+  const int mc = min(max(main_count[q], 0), k);
+  for (int e = threadIdx.x; e < k; e += blockDim.x) {
+    const bool v = e < mc;
+    key[e] = v ? (double)main_scores[(size_t)q * k + e] : kRlNegInf;
+    ord[e] = v ? main_ids[(size_t)q * k + e] : kRlNoOrd;
+  }
+}
+
+__global__ __launch_bounds__(kStThreads) void sparse_tail_scan_kernel(
+    const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
+    const float* __restrict__ values, int64_t tail_rows, int64_t ordinal_base,
+    const int32_t* __restrict__ q_indptr, const int32_t* __restrict__ q_indices,
+    const float* __restrict__ q_values, int k, const uint64_t* __restrict__ row_mask,
+    const float* __restrict__ main_scores, const int64_t* __restrict__ main_ids,
+    const int32_t* __restrict__ main_count, const uint32_t* __restrict__ main_flags, int direct,
+    int kc, int32_t* __restrict__ part_cnt, double* __restrict__ part_key,
+    int64_t* __restrict__ part_ord, float* __restrict__ out_scores,
+    int64_t* __restrict__ out_ids, int32_t* __restrict__ out_count,
+    uint32_t* __restrict__ out_flags) {
+  __shared__ int32_t qidx[kMaxTerms];
+  __shared__ float qval[kMaxTerms];
+  __shared__ int64_t ip[kStChunk + 1];
+  __shared__ float row_score[kStChunk];
+  __shared__ int32_t row_hit[kStChunk];
+  __shared__ int32_t wave_cnt[kStWaves];
+  __shared__ double key[kStSort];
+  __shared__ int64_t ord[kStSort];
+  const int q = blockIdx.y;
+  const int chunk = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int64_t c0 = (int64_t)chunk * kStChunk;
+  const int m = (int)max<int64_t>(0, min<int64_t>(kStChunk, tail_rows - c0));
+  const int32_t qa = q_indptr[q];
+  const int nq = max(0, min(q_indptr[q + 1] - qa, kMaxTerms));
+  const int p2 = armi::pow2_at_least(max(nq, 1));
+  const float thr = tail_threshold(main_scores, main_count, q, k);
+
+  if (tid < p2) {
+    qidx[tid] = tid < nq ? q_indices[qa + tid] : 0x7fffffff;
+    qval[tid] = tid < nq ? q_values[qa + tid] : 0.0f;
+  }
+  if (tid <= m && m > 0) ip[tid] = indptr[c0 + tid];
+  if (tid < kStChunk) row_hit[tid] = 0;
+  __syncthreads();
+
+  if (nq > 0) {
+    for (int b = 0; b < kStRowsPerWave; b += kStBatch) {
+      const int e0 = wave * kStRowsPerWave + b;  // wave-uniform
+      if (e0 >= m) break;
+      int64_t pa[kStBatch], pb[kStBatch];
+      int32_t t0[kStBatch][2];
+      float v0[kStBatch][2];
+#pragma unroll
+      for (int u = 0; u < kStBatch; ++u) {
+        const int e = e0 + u;
+        bool on = e < m;
+        if (on && row_mask) on = (row_mask[(c0 + e) >> 6] >> ((c0 + e) & 63)) & 1;
+        pa[u] = tail_uniform(on ? ip[e] : 0);  // (the same for every lane: scalar loop bounds)
+        pb[u] = tail_uniform(on ? ip[e + 1] : 0);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int64_t p = pa[u] + h * 64 + lane;
+          const bool in = p < pb[u];
+          t0[u][h] = in ? indices[p] : -1;
+          v0[u][h] = in ? values[p] : 0.0f;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kStBatch; ++u) {
+        float s = 0.0f;
+        bool any = false;
+        int32_t t[2] = {t0[u][0], t0[u][1]};
+        float v[2] = {v0[u][0], v0[u][1]};
+        for (int64_t p0 = pa[u]; p0 < pb[u]; p0 += 128) {
+          if (p0 != pa[u]) {  // rows past 128 postings: further rounds, one at a time
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+              const int64_t p = p0 + h * 64 + lane;
+              const bool in = p < pb[u];
+              t[h] = in ? indices[p] : -1;
+              v[h] = in ? values[p] : 0.0f;
+            }
+          }
+          int pos[2] = {0, 0};
+          for (int step = p2 >> 1; step > 0; step >>= 1) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) pos[h] += qidx[pos[h] + step - 1] < t[h] ? step : 0;
+          }
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const bool hit = t[h] >= 0 && pos[h] < nq && qidx[pos[h]] == t[h];
+            const float prod = __fmul_rn(qval[pos[h]], v[h]);
+            unsigned long long hits = __ballot(hit);
+            any |= hits != 0;
+            while (hits) {  // ascending lane order = ascending term order
+              const int l = __builtin_ctzll(hits);
+              s = __fadd_rn(s, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(prod), l)));
+              hits &= hits - 1;
+            }
+          }
+        }
+        if (lane == 0 && e0 + u < m) {
+          row_score[e0 + u] = s;
+          row_hit[e0 + u] = any && s >= thr;
+        }
+      }
+    }
+  }
+  __syncthreads();
+
+  // survivors in row order behind the main list (direct) or at the front (chunk list)
+  const bool sv = tid < m && row_hit[tid];
+  const unsigned long long svm = __ballot(sv);
+  if (lane == 0) wave_cnt[wave] = __popcll(svm);
+  const int base = direct ? k : 0;
+  if (direct) tail_load_main(key, ord, main_scores, main_ids, main_count, q, k);
+  __syncthreads();
+  int at = __popcll(svm & ((1ull << lane) - 1));
+  int cnt = 0;
+#pragma unroll
+  for (int w = 0; w < kStWaves; ++w) {
+    at += w < wave ? wave_cnt[w] : 0;
+    cnt += wave_cnt[w];
+  }
+  if (sv) {
+    key[base + at] = (double)row_score[tid];
+    ord[base + at] = ordinal_base + c0 + tid;
+  }
+  if (direct || cnt > kc) {
+    const int n = armi::pow2_at_least(max(base + cnt, 2));
+    for (int e = base + cnt + tid; e < n; e += kStThreads) {
+      key[e] = kRlNegInf;
+      ord[e] = kRlNoOrd;
+    }
+    armi::lds_sort_rank_desc(key, ord, n);
+  } else {
+    __syncthreads();
+  }
+  if (direct) {
+    tail_write_out(key, ord, q, k, main_flags, out_scores, out_ids, out_count, out_flags);
+    return;
+  }
+  cnt = min(cnt, kc);
+  const size_t slot = (size_t)q * gridDim.x + chunk;
+  if (tid == 0) part_cnt[slot] = cnt;
+  for (int c = tid; c < cnt; c += kStThreads) {
+    part_key[slot * kc + c] = key[c];
+    part_ord[slot * kc + c] = ord[c];
+  }
+}
+
+// One workgroup per query: [0, k) holds the best so far (first the main list), the chunk lists'
+// entries are gathered behind it, kStFinish - k at a time, and one bitonic sort per round keeps
+// the best k in front. The counts of kStGroup chunks are prefix-summed together so that the
+// gather is dense whatever the chunks hold. chunks == 0 (an empty tail) copies the main list.
+__global__ __launch_bounds__(kStThreads) void sparse_tail_finish_kernel(
+    const int32_t* __restrict__ part_cnt, const double* __restrict__ part_key,
+    const int64_t* __restrict__ part_ord, int chunks, int kc, int k,
+    const float* __restrict__ main_scores, const int64_t* __restrict__ main_ids,
+    const int32_t* __restrict__ main_count, const uint32_t* __restrict__ main_flags,
+    float* __restrict__ out_scores, int64_t* __restrict__ out_ids,
+    int32_t* __restrict__ out_count, uint32_t* __restrict__ out_flags) {
+  __shared__ double key[kStFinish];
+  __shared__ int64_t ord[kStFinish];
+  __shared__ int32_t pre[kStGroup + 1];
+  __shared__ int32_t wave_sum[kStWaves];
+  const int q = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int cap = kStFinish - k;
+  tail_load_main(key, ord, main_scores, main_ids, main_count, q, k);
+  int fill = 0;  // entries gathered behind [0, k) since the last sort (workgroup-uniform)
+  for (int g0 = 0; g0 < chunks; g0 += kStGroup) {
+    const int ng = min(kStGroup, chunks - g0);
+    // inclusive prefix of the group's counts
+    int c = tid < ng ? min(max(part_cnt[(size_t)q * chunks + g0 + tid], 0), kc) : 0;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int o = __shfl_up(c, d);
+      if (lane >= d) c += o;
+    }
+    __syncthreads();  // the previous group's pre[] is no longer read
+    if (lane == 63) wave_sum[wave] = c;
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < kStWaves; ++w) c += w < wave ? wave_sum[w] : 0;
+    pre[tid + 1] = c;
+    if (tid == 0) pre[0] = 0;
+    __syncthreads();
+    const int gt = pre[ng];
+    for (int done = 0; done < gt;) {
+      const int take = min(cap - fill, gt - done);
+      for (int e = tid; e < take; e += kStThreads) {
+        const int t = done + e;
+        int lo = 0, hi = ng;  // pre[lo] <= t < pre[hi]
+        while (hi - lo > 1) {
+          const int mid = (lo + hi) >> 1;
+          if (pre[mid] <= t) lo = mid; else hi = mid;
+        }
+        const size_t src = ((size_t)q * chunks + g0 + lo) * kc + (t - pre[lo]);
+        key[k + fill + e] = part_key[src];
+        ord[k + fill + e] = part_ord[src];
+      }
+      fill += take;
+      done += take;
+      if (fill == cap) {
+        armi::lds_sort_rank_desc(key, ord, kStFinish);
+        fill = 0;
+      }
+    }
+  }
+  if (fill > 0) {  // (fill == 0: [0, k) is sorted, by the last round or as the main list came)
+    const int n = armi::pow2_at_least(k + fill);
+    for (int e = k + fill + tid; e < n; e += kStThreads) {
+      key[e] = kRlNegInf;
+      ord[e] = kRlNoOrd;
+    }
+    armi::lds_sort_rank_desc(key, ord, n);
+  } else {
+    __syncthreads();
+  }
+  tail_write_out(key, ord, q, k, main_flags, out_scores, out_ids, out_count, out_flags);
+}
+
+int64_t tail_chunks(int64_t tail_rows) { return (tail_rows + kStChunk - 1) / kStChunk; }
+
 }  // namespace
 
 extern "C" {
@@ -2056,6 +2364,64 @@ int armi_sparse_rowlist_topk(const int64_t* indptr, const int32_t* indices, cons
       part_key, part_ord, chunks, k, list_ptr, q_list, n_lists, max_list_rows, out_scores, out_ids,
       out_count, out_flags);
   ARMI_LAUNCHED("sparse_rowlist_merge_kernel");
+  return ARMI_OK;
+}
+
+int armi_sparse_tail_chunk_rows(void) { return kStChunk; }
+
+size_t armi_sparse_tail_workspace_bytes(int64_t tail_rows, int n_queries, int k) {
+  if (tail_rows <= 0 || n_queries <= 0 || k <= 0) return 0;
+  const size_t chunks = (size_t)tail_chunks(tail_rows);
+  if (chunks == 1) return 0;  // one chunk: the scan workgroups write the outputs, no workspace
+  const size_t kc = (size_t)std::min(std::min(k, kMaxK), kStChunk);
+  return armi::align_up((size_t)n_queries * chunks * 4, 256) +
+         2 * armi::align_up((size_t)n_queries * chunks * kc * 8, 256) + 256;
+}
+
+int armi_sparse_tail_topk(const int64_t* indptr, const int32_t* indices, const float* values,
+                          int64_t tail_rows, int64_t ordinal_base, const int32_t* q_indptr,
+                          const int32_t* q_indices, const float* q_values, int n_queries, int k,
+                          const uint64_t* tail_row_mask, const float* main_scores,
+                          const int64_t* main_ids, const int32_t* main_count,
+                          const uint32_t* main_flags, float* out_scores, int64_t* out_ids,
+                          int32_t* out_count, uint32_t* out_flags, void* workspace,
+                          size_t workspace_bytes, hipStream_t stream) {
+  ARMI_REQUIRE(tail_rows >= 0, "armi_sparse_tail_topk: tail_rows < 0");
+  ARMI_REQUIRE(tail_chunks(tail_rows) <= 0x7fffffff,
+               "armi_sparse_tail_topk: tail_rows too large for one call");
+  ARMI_REQUIRE(n_queries >= 0 && n_queries <= 65535,
+               "armi_sparse_tail_topk: n_queries must be in [0, 65535]");
+  ARMI_REQUIRE(k >= 1 && k <= kMaxK, "armi_sparse_tail_topk: k must be in [1, 240]");
+  if (n_queries == 0) return ARMI_OK;
+  // (indices / values may be null for a tail without postings, the query term arrays are not
+  // read for queries without terms, the workspace is not used by a tail of at most one chunk)
+  ARMI_REQUIRE((indptr || tail_rows == 0) && q_indptr && main_scores && main_ids && main_count &&
+                   out_scores && out_ids && out_count,
+               "armi_sparse_tail_topk: null pointer argument");
+  const size_t need = armi_sparse_tail_workspace_bytes(tail_rows, n_queries, k);
+  ARMI_REQUIRE(workspace_bytes >= need && (workspace || need == 0),
+               "armi_sparse_tail_topk: workspace too small");
+  ARMI_REQUIRE(out_scores != main_scores && out_ids != main_ids && out_count != main_count,
+               "armi_sparse_tail_topk: outputs must not alias the main list");
+  const int chunks = (int)tail_chunks(tail_rows);
+  const int direct = chunks == 1;
+  const int kc = std::min(k, kStChunk);
+  armi::Carver cv(workspace);
+  int32_t* part_cnt = cv.take<int32_t>(chunks > 1 ? (size_t)n_queries * chunks : 0);
+  double* part_key = cv.take<double>(chunks > 1 ? (size_t)n_queries * chunks * kc : 0);
+  int64_t* part_ord = cv.take<int64_t>(chunks > 1 ? (size_t)n_queries * chunks * kc : 0);
+  if (chunks > 0) {
+    sparse_tail_scan_kernel<<<dim3(chunks, n_queries), dim3(kStThreads), 0, stream>>>(
+        indptr, indices, values, tail_rows, ordinal_base, q_indptr, q_indices, q_values, k,
+        tail_row_mask, main_scores, main_ids, main_count, main_flags, direct, kc, part_cnt,
+        part_key, part_ord, out_scores, out_ids, out_count, out_flags);
+    ARMI_LAUNCHED("sparse_tail_scan_kernel");
+    if (direct) return ARMI_OK;
+  }
+  sparse_tail_finish_kernel<<<dim3(n_queries), dim3(kStThreads), 0, stream>>>(
+      part_cnt, part_key, part_ord, chunks, kc, k, main_scores, main_ids, main_count, main_flags,
+      out_scores, out_ids, out_count, out_flags);
+  ARMI_LAUNCHED("sparse_tail_finish_kernel");
   return ARMI_OK;
 }
 

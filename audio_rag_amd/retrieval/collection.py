@@ -12,8 +12,10 @@ rebuild never frees an index a running search still holds (the old handles die w
 reference).
 
 Live ingest (live_tail_rows > 0): after the first build, later upserts are flushed into a small
-growable fp16 segment, the tail (TailIndex + a SparseIndex over the tail's rows only), which
-every search covers together with the main indexes; the main indexes are not touched by a flush.
+growable segment, the tail (TailIndex: fp16 rows; TailSparseIndex: the rows' forward CSR, appended
+to on the device, with no inverted index of its own), which every search covers together with the
+main indexes by the fused tail passes; the main indexes are not touched by a flush, and a flush
+uploads the new points only.
 When a flush would pass the tail's capacity the tail is folded into new main indexes built from
 device-side concatenations (compact()). A flush changes the tail in place on the current stream:
 searches on other streams must not overlap an upsert's first search.
@@ -29,7 +31,7 @@ from dataclasses import dataclass, field
 import numpy as np
 import torch
 
-from audio_rag_amd.retrieval.device import DenseIndex, SparseIndex, TailIndex
+from audio_rag_amd.retrieval.device import DenseIndex, SparseIndex, TailIndex, TailSparseIndex
 
 BGE_M3_VOCAB = 250002
 
@@ -38,7 +40,8 @@ _NO_MATCH = object()
 
 # The device segments of a collection: the main indexes over ordinals [base, base + main_rows)
 # and, in a live collection, the tail over the ordinals behind them (tail None or tail.n_rows == 0:
-# nothing to search there; tail_sparse None in a dense-only collection).
+# nothing to search there; tail_sparse, a TailSparseIndex holding the same rows' forward CSR, None in
+# a dense-only collection).
 Segments = namedtuple("Segments", "dense sparse tail tail_sparse main_rows")
 
 
@@ -113,7 +116,7 @@ class ChunkCollection:
     # live ingest (RetrievalConfig.live_tail_rows; 0 = rebuild on every add)
     live_tail_rows: int = 0
     _tail: TailIndex | None = None
-    _tail_sparse: SparseIndex | None = None
+    _tail_sparse: TailSparseIndex | None = None
     _main_rows: int = 0      # points held by the main indexes
     _vmax: int = -1          # largest sparse term id upserted so far
     _seg_mask_cache: dict = field(default_factory=dict)
@@ -255,8 +258,8 @@ class ChunkCollection:
 
     def _flush_live(self) -> None:
         """Brings the points upserted since the last build into the tail (lock held): uploads
-        only their fp16 rows, appends them, and rebuilds the tail's sparse index over the tail's
-        rows. When they would not fit, the tail is folded into the main indexes first (and the new
+        only their fp16 rows and their CSR and appends both (no native sparse index is built
+        here). When they would not fit, the tail is folded into the main indexes first (and the new
         points with it when they alone exceed a tail)."""
         lo, hi = self._built_rows, self.count
         self._graphs = {}
@@ -283,10 +286,10 @@ class ChunkCollection:
             self._tail = TailIndex(self.dim, cap, self._main_rows, self.device)
         self._tail.append(new)
         if self.hybrid:
-            base = self._main_rows
-            indptr, idx, val = (self._upload(a) for a in self._host_csr(base, hi))
-            self._tail_sparse = SparseIndex(indptr, idx, val, max(BGE_M3_VOCAB, self._vmax + 1),
-                                            ordinal_base=base)
+            if self._tail_sparse is None:
+                self._tail_sparse = TailSparseIndex(self._main_rows, self.device)
+            self._tail_sparse.append(*(self._upload(a) for a in self._host_csr(lo, hi)),
+                                     vocab=max(BGE_M3_VOCAB, self._vmax + 1))
         self._built_rows = hi
 
     def compact(self) -> None:

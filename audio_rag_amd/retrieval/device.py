@@ -7,6 +7,8 @@ memory and the stream. Results stay on the device until the caller materialises 
 from __future__ import annotations
 
 import ctypes
+import os
+import threading
 
 import torch
 
@@ -421,6 +423,168 @@ class SparseIndex:
                  ptr(out.scores), ptr(out.ids), ptr(out.count), ptr(out.flags), ptr(workspace),
                  workspace.numel(), stream_handle())
         return out
+
+
+def csr_append(indptr: torch.Tensor | None, indices: torch.Tensor | None,
+               values: torch.Tensor | None, new_indptr: torch.Tensor, new_indices: torch.Tensor,
+               new_values: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The CSR of `rows + new rows`: (indptr int64, indices int32, values float32), the new block
+    given as a CSR of its own (new_indptr starts at 0). indptr None = the first append. Tensors of
+    any one device; the last offset is added as a tensor, so nothing is read back to the host."""
+    if new_indptr.dtype != torch.int64 or new_indptr.dim() != 1 or new_indptr.numel() < 1:
+        raise ValueError("new_indptr must be a 1-D int64 tensor of n + 1 offsets")
+    if new_indices.dtype != torch.int32 or new_values.dtype != torch.float32 or \
+            new_indices.shape != new_values.shape or new_indices.dim() != 1:
+        raise ValueError("new_indices / new_values must be 1-D int32 / float32 of one length")
+    if indptr is None:
+        return new_indptr.clone(), new_indices.clone(), new_values.clone()
+    return (torch.cat([indptr, new_indptr[1:] + indptr[-1:]]), torch.cat([indices, new_indices]),
+            torch.cat([values, new_values]))
+
+
+class TailSparseIndex:
+    """The sparse side of a live collection's tail: the forward CSR of the rows added since the
+    last compaction, on the device, and nothing else. append() extends it with the new rows' CSR
+    (a device-side concatenation); tail_topk() is the fused pass that extends a finished list of
+    the main SparseIndex by these rows (armi_sparse_tail_topk reads the CSR directly);
+    topk_rows() is SparseIndex's row-list search, which needs the forward CSR only. topk(), the
+    general search over the tail alone, runs on a native SparseIndex built on first use and
+    dropped by the next append (general_built tells whether one exists): no flush and no fused
+    search pays for an inverted index over rows that are folded into the main index soon.
+
+    A search takes one snapshot of (indptr, indices, values, n_rows): an append replaces the
+    snapshot, it never writes into arrays a search may be reading."""
+
+    def __init__(self, ordinal_base: int, device: torch.device, vocab: int = 1):
+        self.ordinal_base = int(ordinal_base)
+        self.device = device
+        self.vocab = int(vocab)
+        self._csr = (torch.zeros(1, dtype=torch.int64, device=device),
+                     torch.zeros(0, dtype=torch.int32, device=device),
+                     torch.zeros(0, dtype=torch.float32, device=device), 0)
+        self._general: SparseIndex | None = None
+        self._lock = threading.Lock()
+
+    indptr = property(lambda self: self._csr[0])
+    indices = property(lambda self: self._csr[1])
+    values = property(lambda self: self._csr[2])
+    n_rows = property(lambda self: self._csr[3])
+
+    @property
+    def general_built(self) -> bool:
+        """Whether a native SparseIndex over the tail's rows exists now (topk() builds one)."""
+        return self._general is not None
+
+    def append(self, indptr: torch.Tensor, indices: torch.Tensor, values: torch.Tensor,
+               vocab: int | None = None) -> None:
+        """Adds the rows of a CSR of their own (indptr from 0; device tensors) behind the current
+        end, on the current stream. vocab: the vocabulary the general index is built with from
+        now on (it only grows)."""
+        for t in (indptr, indices, values):
+            if not t.is_cuda:
+                raise ValueError("the appended CSR must live on the GPU")
+        with self._lock:  # (two appends never interleave; searches read one snapshot, unlocked)
+            old = self._csr
+            first = old[3] == 0
+            csr = csr_append(None if first else old[0], old[1], old[2], indptr, indices, values)
+            self._csr = (*csr, old[3] + int(indptr.numel()) - 1)
+            if vocab is not None:
+                self.vocab = max(self.vocab, int(vocab))
+            # (not closed: a search that fetched it may still be using it; it dies with its last
+            # reference)
+            self._general = None
+
+    def close(self) -> None:
+        with self._lock:
+            general, self._general = self._general, None
+        if general is not None:
+            general.close()
+
+    def _general_index(self) -> "SparseIndex":
+        with self._lock:
+            if self._general is None:
+                indptr, indices, values, _ = self._csr
+                vocab = max(self.vocab, 1)
+                self._general = SparseIndex(indptr, indices, values, vocab,
+                                            ordinal_base=self.ordinal_base)
+            return self._general
+
+    def topk(self, q_indptr: torch.Tensor, q_indices: torch.Tensor, q_values: torch.Tensor, k: int,
+             row_mask: torch.Tensor | None = None, workspace: torch.Tensor | None = None) -> TopK:
+        """SparseIndex.topk over the tail's rows alone (builds the native index when missing)."""
+        return self._general_index().topk(q_indptr, q_indices, q_values, k, row_mask=row_mask,
+                                          workspace=workspace)
+
+    @staticmethod
+    def chunk_rows() -> int:
+        """Tail rows one scan workgroup of the fused pass covers."""
+        return int(query("armi_sparse_tail_chunk_rows"))
+
+    def tail_workspace_bytes(self, n_queries: int, k: int) -> int:
+        return int(query("armi_sparse_tail_workspace_bytes", self.n_rows, n_queries, k))
+
+    def tail_topk(self, q_indptr: torch.Tensor, q_indices: torch.Tensor, q_values: torch.Tensor,
+                  k: int, main: TopK, row_mask: torch.Tensor | None = None,
+                  workspace: torch.Tensor | None = None) -> TopK:
+        """The top-k over the main index and this segment, from `main` = the main SparseIndex's
+        topk of the same queries and k (armi_sparse_tail_topk). row_mask: bit r = row r of this
+        segment. ARMI_TAIL_PASS=general (read per call) computes the same answer by topk() over
+        the tail and a merge of the two lists."""
+        if not 1 <= k <= MAX_K:
+            raise ValueError(f"k must be in [1, {MAX_K}]")
+        for t, dt, name in ((q_indptr, torch.int32, "q_indptr"), (q_indices, torch.int32, "q_indices"),
+                            (q_values, torch.float32, "q_values")):
+            if t.dtype != dt or t.dim() != 1 or not t.is_cuda or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous 1-D {dt} device tensor")
+        b = int(q_indptr.numel()) - 1
+        indptr, indices, values, n_rows = self._csr
+        dev = indptr.device
+        for t, dt, shape, name in ((main.ids, torch.int64, (b, k), "ids"),
+                                   (main.scores, torch.float32, (b, k), "scores"),
+                                   (main.count, torch.int32, (b,), "count"),
+                                   (main.flags, torch.int32, (b,), "flags")):
+            if name == "flags" and t is None:
+                continue
+            if b < 0 or not isinstance(t, torch.Tensor) or t.dtype != dt or \
+                    tuple(t.shape) != shape or t.device != dev:
+                raise ValueError("main must be the main index's top-k of the same queries and k "
+                                 f"on {dev} (its {name} is not a {dt} tensor of shape {shape} there)")
+        if q_indptr.device != dev:
+            raise ValueError(f"the query CSR must live on {dev}")
+        if row_mask is not None:
+            need = (n_rows + 63) // 64
+            if row_mask.dtype != torch.int64 or row_mask.numel() < need or \
+                    row_mask.device != dev or not row_mask.is_contiguous():
+                raise ValueError(f"row_mask must be a contiguous int64 tensor of >= {need} words "
+                                 f"on {dev}")
+        if os.environ.get("ARMI_TAIL_PASS", "")[:1] == "g":
+            t = self.topk(q_indptr, q_indices, q_values, k, row_mask=row_mask)
+            scores = torch.stack([main.scores, t.scores])
+            m = merge_shards(scores.double(), scores, torch.stack([main.ids, t.ids]),
+                             torch.stack([main.count, t.count]), k)
+            m.flags = main.flags
+            return m
+        out = TopK(scores=torch.empty((b, k), dtype=torch.float32, device=dev),
+                   ids=torch.empty((b, k), dtype=torch.int64, device=dev),
+                   count=torch.empty(b, dtype=torch.int32, device=dev),
+                   flags=torch.empty(b, dtype=torch.int32, device=dev))
+        if b == 0:
+            return out
+        need = int(query("armi_sparse_tail_workspace_bytes", n_rows, b, k))
+        if workspace is None or workspace.numel() < need:
+            workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        m_scores, m_ids, m_count = (t.contiguous() for t in (main.scores, main.ids, main.count))
+        m_flags = None if main.flags is None else main.flags.contiguous()
+        with torch.cuda.device(dev):
+            call("armi_sparse_tail_topk", ptr(indptr), ptr(indices), ptr(values), n_rows,
+                 self.ordinal_base, ptr(q_indptr), ptr(q_indices), ptr(q_values), b, k,
+                 ptr(row_mask), ptr(m_scores), ptr(m_ids), ptr(m_count), ptr(m_flags),
+                 ptr(out.scores), ptr(out.ids), ptr(out.count), ptr(out.flags), ptr(workspace),
+                 workspace.numel(), stream_handle())
+        return out
+
+    rowlist_workspace_bytes = staticmethod(SparseIndex.rowlist_workspace_bytes)
+    topk_rows = SparseIndex.topk_rows  # reads indptr / indices / values / n_rows / ordinal_base
 
 
 def merge_shards(rank: torch.Tensor, scores: torch.Tensor, ids: torch.Tensor, count: torch.Tensor,

@@ -487,7 +487,7 @@ class MI355XRetriever(BaseRetriever):
                          tail: tuple | None) -> TopK:
         """The row-list groups of a planned call (_encode_rowlists' lists, the queries in the same
         order): one dense and one sparse launch per segment, the segments' lists merged exactly
-        (merge_shards, as _search_device merges the sparse segments), hybrid through the same RRF.
+        (merge_shards: rank = the exact key), hybrid through the same RRF.
         Device work only (graph-capturable)."""
         from audio_rag_amd.retrieval.device import merge_shards
 
@@ -582,11 +582,9 @@ class MI355XRetriever(BaseRetriever):
                        masks: tuple | None) -> TopK:
         """The device work of search_batch for a resolved collection and branch. masks:
         ChunkCollection.segment_masks (main mask, tail mask) or None. Both segments of a live
-        collection are searched: dense by the main top-k followed by the fused tail pass, sparse
-        by both indexes' top-k merged exactly (rank = score, as the sharded search merges); an
-        empty tail adds no kernel."""
-        from audio_rag_amd.retrieval.device import merge_shards
-
+        collection are searched, dense and sparse alike: the main top-k followed by the fused
+        tail pass (TailIndex.tail_topk, TailSparseIndex.tail_topk); an empty tail adds no
+        kernel."""
         seg = coll.segments()
         mask, tmask = masks if masks is not None else (None, None)
         live = seg.tail is not None and seg.tail.n_rows > 0
@@ -598,14 +596,7 @@ class MI355XRetriever(BaseRetriever):
 
         def sparse(k: int) -> TopK:
             s = seg.sparse.topk(*sq, k, row_mask=mask)
-            if not live:
-                return s
-            t = seg.tail_sparse.topk(*sq, k, row_mask=tmask)
-            scores = torch.stack([s.scores, t.scores])
-            m = merge_shards(scores.double(), scores, torch.stack([s.ids, t.ids]),
-                             torch.stack([s.count, t.count]), k)
-            m.flags = s.flags
-            return m
+            return seg.tail_sparse.tail_topk(*sq, k, s, row_mask=tmask) if live else s
 
         if mode == "hybrid":
             if self._hybrid is None:

@@ -58,8 +58,8 @@ extern "C" {
  * must not bind this library (armi_abi_version() tells). 3: growable fp16 segments
  * (armi_index_create_tail / _append / _capacity) and armi_dense_tail_topk; nothing removed.
  * 4: row-list top-k (armi_dense_rowlist_topk, armi_sparse_rowlist_topk, ARMI_FLAG_ROWLIST);
- * nothing removed. */
-#define ARMI_ABI_VERSION 4
+ * nothing removed. 5: armi_sparse_tail_topk (+ _workspace_bytes, _chunk_rows); nothing removed. */
+#define ARMI_ABI_VERSION 5
 
 /* flags written per query by the top-k entry points */
 #define ARMI_FLAG_CERTIFIED 1u /* fast path proved its top-k equal to the exact ranking */
@@ -399,6 +399,34 @@ int armi_sparse_rowlist_topk(const int64_t* indptr, const int32_t* indices, cons
                              float* out_scores, int64_t* out_ids, int32_t* out_count,
                              uint32_t* out_flags, void* workspace, size_t workspace_bytes,
                              hipStream_t stream);
+
+/* Global sparse top-k over a main index and a live tail, from the main index's finished list for
+ * the same queries and k (the sparse counterpart of armi_dense_tail_topk). The tail is a forward
+ * CSR in device memory, armi_sparse_rowlist_topk's encoding (indptr int64 [tail_rows + 1], indices
+ * int32 ascending per row, values float); no armi_sparse_index is involved. Scores are
+ * armi_sparse_topk's: the merge join of the row's and the query's ascending indices from +0.0f,
+ * fl32(q*d) per shared index added in fp32 in ascending index order (mul and add rounded
+ * separately); a query is scored on its first 256 terms, as armi_sparse_topk scores it. A tail row
+ * is a result when it shares at least one index with the query (also with a zero or negative
+ * score) and its bit of tail_row_mask (bit r = tail row r; nullable) is set; a query without terms
+ * adds no tail row. Output: the top k of (main list + tail results) by (score desc, ordinal asc),
+ * ordinal = ordinal_base + row; -1 / -inf past out_count = min(k, main_count + tail results);
+ * out_flags[q] = main_flags[q] (0 when main_flags is null; out_flags nullable): tail scores are
+ * exact and add no bit. Outputs must not alias the main list. k 1..240, n_queries <= 65535, any
+ * tail_rows >= 0 (0 copies the main list). No host synchronisation, graph-capture safe, at most
+ * two launches: one workgroup scans _chunk_rows() tail rows for one query, a tail of one chunk is
+ * finished by its scan workgroup. _workspace_bytes() is 0 for a tail of at most one chunk (and for
+ * empty inputs): the call then reads no workspace and accepts a null pointer with size 0. */
+size_t armi_sparse_tail_workspace_bytes(int64_t tail_rows, int n_queries, int k);
+int armi_sparse_tail_chunk_rows(void);
+int armi_sparse_tail_topk(const int64_t* indptr, const int32_t* indices, const float* values,
+                          int64_t tail_rows, int64_t ordinal_base, const int32_t* q_indptr,
+                          const int32_t* q_indices, const float* q_values, int n_queries, int k,
+                          const uint64_t* tail_row_mask, const float* main_scores,
+                          const int64_t* main_ids, const int32_t* main_count,
+                          const uint32_t* main_flags, float* out_scores, int64_t* out_ids,
+                          int32_t* out_count, uint32_t* out_flags, void* workspace,
+                          size_t workspace_bytes, hipStream_t stream);
 
 /* Enables (1) or disables (0) the MFMA filter of armi_sparse_topk on this index (default on:
  * the exact scan alone when off); usable (host, nullable) = 1 when the index can use the filter

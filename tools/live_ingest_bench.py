@@ -10,13 +10,19 @@ rebuilds the indexes on the next search) and by one with the knob on.
   (c) armi_dense_tail_topk alone at those tail sizes: the fused pass against the forced general
       path (ARMI_TAIL_PASS=general)
   (d) one compaction of a full tail
+  (e) the sparse stage alone, 64 queries at k = 5 and k = 40: the main SparseIndex.topk, and with a
+      tail the main top-k followed by armi_sparse_tail_topk, against the forced general path
+      (ARMI_TAIL_PASS=general: a native index over the tail + the list merge)
 
 Times are host clocks around work that ends in a device synchronise. Every step is timed twice:
 eagerly (search_batch as a caller runs it: Python and launch work included, which bounds these
 sub-0.1-ms steps) and replayed from a HIP graph (the GPU's time for the same kernels). The result is merged into
 --out (JSON, one entry per row count).
 
-    python tools/live_ingest_bench.py --rows 100000 --out profiles/live_ingest.json
+    python tools/live_ingest_bench.py --rows 100000 --out profiles/live_ingest_sparse_tail.json
+
+--parent-json FILE stores another tree's (a) and (b) of the same row count (its own run of this tool,
+in the same session on the same box) under the entry's "parent" key, for the comparison.
 """
 
 from __future__ import annotations
@@ -103,7 +109,9 @@ def main() -> None:
     ap.add_argument("--tail", type=int, default=2048, help="live_tail_rows (capacity = twice)")
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--out", default="profiles/live_ingest.json")
+    ap.add_argument("--out", default="profiles/live_ingest_sparse_tail.json")
+    ap.add_argument("--parent-json", default=None,
+                    help="another tree's output of this tool: its (a) and (b) go under 'parent'")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("live_ingest_bench needs the GPU")
@@ -153,6 +161,7 @@ def main() -> None:
     # (b), (c): tail empty / quarter / full (both retrievers hold the same points)
     on.collection().compact()
     res["b_steps_ms"], res["b_graph_steps_ms"], res["c_tail_pass_ms"] = {}, {}, {}
+    res["e_sparse_stage_ms"] = {}
     for label, target in (("empty", 0), ("quarter", cap // 4), ("full", cap)):
         seg = on.collection().segments()
         have = seg.tail.n_rows if seg.tail is not None else 0
@@ -206,10 +215,46 @@ def main() -> None:
             c["tail_rows"] = target
             res["c_tail_pass_ms"][label] = c
 
+        # (e) the sparse stage alone
+        e = {"tail_rows": target}
+        for k in (5, 40):
+            sws = torch.empty(max(seg.sparse.workspace_bytes(64, k), 1), dtype=torch.uint8, device=dev)
+
+            def main_only(k=k, sws=sws):
+                return seg.sparse.topk(qi, qx, qv, k, workspace=sws)
+
+            fns = {"main": main_only}
+            if target:
+                ts = seg.tail_sparse
+                tws = torch.empty(max(ts.tail_workspace_bytes(64, k), 1), dtype=torch.uint8,
+                                  device=dev)
+
+                def fused(k=k, tws=tws, ts=ts, main_only=main_only):
+                    return ts.tail_topk(qi, qx, qv, k, main_only(), workspace=tws)
+
+                def general(k=k, ts=ts, main_only=main_only):
+                    os.environ["ARMI_TAIL_PASS"] = "general"
+                    out = ts.tail_topk(qi, qx, qv, k, main_only())
+                    del os.environ["ARMI_TAIL_PASS"]
+                    return out
+
+                fns.update(fused=fused, general=general)
+                e[f"k{k}_equal"] = bool(torch.equal(fused().ids, general().ids) and
+                                        torch.equal(fused().scores, general().scores))
+            e[f"k{k}"] = step_ms(fns, dev, args.steps, args.warmup)
+            e[f"k{k}"]["graph"] = step_ms({name: graphed(fn, dev) for name, fn in fns.items()}, dev,
+                                          args.steps, args.warmup)
+        res["e_sparse_stage_ms"][label] = e
+
     # (d) one compaction of the full tail
     res["d_compaction_s"] = timed(lambda: on.collection().compact(), dev)
     res["rows_after"] = on.count()
 
+    if args.parent_json:
+        parent = json.loads(Path(args.parent_json).read_text()).get(str(n), {})
+        res["parent"] = {key: parent[key] for key in ("a_add_to_first_result_s", "b_steps_ms",
+                                                      "b_graph_steps_ms", "first_build_s")
+                         if key in parent}
     out = Path(args.out)
     merged = json.loads(out.read_text()) if out.exists() else {}
     merged[str(n)] = res
