@@ -31,10 +31,13 @@
 #include <vector>
 
 #include "armi_index.h"
+#include "armi_rank_list.h"
 
 namespace {
 
 using armi::TILE_ROWS;
+using armi::kNegInfD;
+using armi::kNoOrd;
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -50,8 +53,6 @@ constexpr int kLaneList = 4;  // top entries kept per lane and query
 constexpr int kKW = 16;       // candidates per workgroup and query
 constexpr int kDepth = 4;     // 64-byte groups in flight per lane
 constexpr float kNegInf = -std::numeric_limits<float>::infinity();
-constexpr double kNegInfD = -std::numeric_limits<double>::infinity();
-constexpr int64_t kNoOrd = std::numeric_limits<int64_t>::max();
 constexpr int kMaxK = 240;
 constexpr int kMergeThreads = 256;
 constexpr int kDenseMergeThreads = 512;  // dense_merge_kernel: 8 waves share the exact rescore
@@ -1411,6 +1412,23 @@ __device__ __forceinline__ int64_t wave_dot_exact(const int32_t (&qf)[DIM / 64],
   return dot_fixed<DIM>(qf, raw);
 }
 
+// Exact sum of squares of the 2^24-scaled query whose slices the wave's lanes hold (in every lane;
+// integer sums: any order gives the same bits), and 1 / |q| of it (0 for a zero query): the factor
+// that turns a rank key into a cosine. Every kernel that writes scores takes it from here, so the
+// scores of one query agree bit for bit whichever kernel finishes it.
+template <int DIM>
+__device__ __forceinline__ int64_t query_norm2(const int32_t (&qf)[DIM / 64]) {
+  int64_t acc = 0;
+#pragma unroll
+  for (int i = 0; i < DIM / 64; ++i) acc += (int64_t)qf[i] * (int64_t)qf[i];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += armi::xor_stride(acc, off);
+  return acc;
+}
+__device__ __forceinline__ double inv_sqrt_norm2(int64_t n2q) {
+  return n2q > 0 ? 1.0 / sqrt((double)n2q) : 0.0;
+}
+
 // Per-query exact norm: writes 1/sqrt(norm2) (0 for a zero query) and |q| in real units.
 template <int DIM>
 __global__ __launch_bounds__(64) void query_norms_kernel(const uint16_t* __restrict__ queries,
@@ -1421,13 +1439,9 @@ __global__ __launch_bounds__(64) void query_norms_kernel(const uint16_t* __restr
   const int lane = threadIdx.x;
   int32_t qf[DIM / 64];
   load_fixed<DIM>(queries + (size_t)q * DIM, lane, qf);
-  int64_t acc = 0;
-#pragma unroll
-  for (int i = 0; i < DIM / 64; ++i) acc += (int64_t)qf[i] * (int64_t)qf[i];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += armi::xor_stride(acc, off);
+  const int64_t acc = query_norm2<DIM>(qf);
   if (lane == 0) {
-    inv_q[q] = acc > 0 ? 1.0 / sqrt((double)acc) : 0.0;
+    inv_q[q] = inv_sqrt_norm2(acc);
     qnorm_real[q] = sqrt((double)acc) * (1.0 / 16777216.0);
   }
 }
@@ -1508,6 +1522,44 @@ __device__ __forceinline__ void exact_keys8(const int32_t (&qf)[DIM / 64],
     }
   }
   key = row >= 0 ? (double)dot * myinv : kNegInfD;
+}
+
+// exact_keys8 for the rank lists: the entries of rows rr[0 .. n) (n <= 8) stored at key / ord
+// [0, n), a row that does not rank (rr[j] < 0) as the empty entry. Slots from n on are not touched.
+template <int DIM>
+__device__ __forceinline__ void store_keys8(const int32_t (&qf)[DIM / 64],
+                                            const uint16_t* __restrict__ rows,
+                                            const double* __restrict__ inv_norm,
+                                            const int32_t (&rr)[8], int n, int64_t ordinal_base,
+                                            int lane, double* key, int64_t* ord) {
+  double kk;
+  int32_t myrow;
+  exact_keys8<DIM>(qf, rows, inv_norm, rr, lane, kk, myrow);
+  const int r = (lane >> 3) & 7;
+  if ((lane & 7) == 0 && r < n) {
+    key[r] = kk;
+    ord[r] = myrow >= 0 ? ordinal_base + myrow : kNoOrd;
+  }
+}
+
+// A chunk of m <= 64 * (waves of the workgroup) entries scored exactly into key / ord [0, m): entry
+// e is row row_of(e), or does not rank when that is negative. Wave w scores entries [64 w, 64 w +
+// 64), eight per round.
+template <int DIM, typename RowOf>
+__device__ __forceinline__ void score_chunk(const int32_t (&qf)[DIM / 64],
+                                            const uint16_t* __restrict__ rows,
+                                            const double* __restrict__ inv_norm, int m,
+                                            int64_t ordinal_base, double* key, int64_t* ord,
+                                            RowOf&& row_of) {
+  const int lane = threadIdx.x & 63;
+  for (int b = 0; b < 64; b += 8) {
+    const int e0 = 64 * armi::wave_id() + b;
+    if (e0 >= m) continue;  // wave-uniform
+    int32_t rr[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) rr[j] = e0 + j < m ? row_of(e0 + j) : -1;
+    store_keys8<DIM>(qf, rows, inv_norm, rr, m - e0, ordinal_base, lane, key + e0, ord + e0);
+  }
 }
 
 // fp32 keys of 8 rows at once, in exact_keys8's layout and key units (2^24 |q| cos). Each lane's
@@ -1647,12 +1699,8 @@ __device__ __forceinline__ void merge_body(
   // exact query norm (every wave holds the fixed-point query for the rescore anyway)
   int32_t qf[DIM / 64];
   load_fixed<DIM>(queries + (size_t)qg * DIM, lane, qf);
-  int64_t n2q = 0;
-#pragma unroll
-  for (int i = 0; i < DIM / 64; ++i) n2q += (int64_t)qf[i] * (int64_t)qf[i];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) n2q += armi::xor_stride(n2q, off);
-  const double inv_q = n2q > 0 ? 1.0 / sqrt((double)n2q) : 0.0;
+  const int64_t n2q = query_norm2<DIM>(qf);
+  const double inv_q = inv_sqrt_norm2(n2q);
   const double qnorm_real = sqrt((double)n2q) * (1.0 / 16777216.0);
   if (tid == 0) {
     // read by the collect merge (agent-scope stores: past this XCD's L2)
@@ -2031,8 +2079,8 @@ constexpr size_t kMergeLds = kSelCap * 8 + 256 * 16 + 64 + 16 + 256 * 4;
 // Second-pass merge, one workgroup per query (certified queries exit at once): exact keys of the
 // rows dense_scan_i8_kernel<COLLECT> appended (local rows -> ordinals), top-k by (key desc,
 // ordinal asc). The list holds every row of the true top-k (see the collect pass), so this top-k
-// is the exact answer. Rows go through LDS 512 at a time: [0, 512) the best so far, [512, 1024)
-// the next chunk, one bitonic sort per chunk; a list of <= 512 rows is scored and sorted once.
+// is the exact answer. Rows go through LDS 512 at a time (armi::merge_stream, armi_rank_list.h); a
+// list of <= 512 rows is scored and sorted once.
 // A query whose list overflowed (more than cap rows within delta + the int8 slack of its k-th key:
 // a pile of near-duplicates) is answered by the grid's n_help helper workgroups instead: helper h
 // scores its 1/n_help of the shard exactly and writes its slice's top-k rows into the query's
@@ -2040,6 +2088,7 @@ constexpr size_t kMergeLds = kSelCap * 8 + 256 * 16 + 64 + 16 + 256 * 4;
 // dense_merge_kernel) merges those n_help * k <= cap rows as above. The shard is read once per
 // such query, spread over n_help CUs. Helpers find nothing to do, and exit, on every other call.
 constexpr int kColChunk = 512;
+static_assert(kColChunk == kDenseMergeThreads, "score_chunk: 64 rows of a chunk per wave");
 constexpr size_t kColMergeLds = 2 * kColChunk * 16 + 16;
 constexpr int kMaxHelp = 64;
 // Per-query capacity of the collect pass's row list (beyond it the second-pass merge scores every
@@ -2047,7 +2096,9 @@ constexpr int kMaxHelp = 64;
 constexpr int kCollectCap = 4096;
 
 // Top of n rows (list entries, or rows r0 .. r0 + n - 1 of the shard when list == nullptr) left
-// sorted by (key desc, ordinal asc) in key / ord [0, max(n, k)); filtered / invalid rows skipped.
+// sorted by (key desc, ordinal asc) in key / ord [0, max(min(n, kColChunk), k)); filtered /
+// invalid rows skipped. The rows stream through armi::merge_stream kColChunk at a time (score_chunk:
+// eight per wave and round); a list of <= kColChunk rows is scored and sorted once.
 template <int DIM>
 __device__ void collect_top_rows(const int32_t* __restrict__ list, int64_t r0, int64_t n, int k,
                                  const int32_t (&qf)[DIM / 64], const uint16_t* __restrict__ rows,
@@ -2055,51 +2106,16 @@ __device__ void collect_top_rows(const int32_t* __restrict__ list, int64_t r0, i
                                  const int64_t* __restrict__ norm2,
                                  const uint64_t* __restrict__ row_mask, int64_t ordinal_base,
                                  double* key, int64_t* ord) {
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = armi::wave_id();
   __syncthreads();  // the caller's previous use of key / ord is over
-  for (int e = tid; e < 2 * kColChunk; e += kDenseMergeThreads) {
-    key[e] = kNegInfD;
-    ord[e] = kNoOrd;
-  }
-  const bool single = n <= kColChunk;
-  constexpr int kPerWave = kColChunk / (kDenseMergeThreads / 64);  // 64 rows per wave and chunk
-  for (int64_t c0 = 0; c0 < n; c0 += kColChunk) {
-    const int base = single ? 0 : kColChunk;
-    const int m = (int)min<int64_t>(kColChunk, n - c0);
-    __syncthreads();  // the previous sort is done with [base, base + kColChunk)
-    for (int b = 0; b < kPerWave; b += 8) {
-      int32_t rr[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int e = kPerWave * wave + b + j;
-        int32_t o = -1;
-        if (e < m) {
-          if (list == nullptr) {
-            const int64_t row = r0 + c0 + e;
-            const bool on = norm2[row] >= 0 &&
-                            (!row_mask || ((row_mask[row >> 6] >> (row & 63)) & 1ull));
-            o = on ? (int32_t)row : -1;
-          } else {
-            o = list[c0 + e];
-          }
-        }
-        rr[j] = o;
-      }
-      double kk;
-      int32_t myrow;
-      exact_keys8<DIM>(qf, rows, inv_norm, rr, lane, kk, myrow);
-      if ((lane & 7) == 0) {
-        const int e = base + kPerWave * wave + b + ((lane >> 3) & 7);
-        key[e] = kk;
-        ord[e] = myrow >= 0 ? ordinal_base + myrow : kNoOrd;
-      }
-    }
-    armi::lds_sort_rank_desc(key, ord,
-                             single ? armi::pow2_at_least(m > k ? m : k) : 2 * kColChunk);
-  }
-  __syncthreads();
+  armi::merge_stream(key, ord, kColChunk, k, n, [&](int64_t c0, int m, double* ck, int64_t* co) {
+    score_chunk<DIM>(qf, rows, inv_norm, m, ordinal_base, ck, co, [&](int e) -> int32_t {
+      if (list != nullptr) return list[c0 + e];
+      const int64_t row = r0 + c0 + e;
+      const bool on =
+          norm2[row] >= 0 && (!row_mask || ((row_mask[row >> 6] >> (row & 63)) & 1ull));
+      return on ? (int32_t)row : -1;
+    });
+  });
 }
 
 template <int DIM>
@@ -2117,25 +2133,10 @@ __device__ __forceinline__ void collect_merge_body(
   int* s_last = reinterpret_cast<int*>(smem + 2 * kColChunk * 16);
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-  const int wave = armi::wave_id();
   auto write_out = [&](int qg) {
-    if (wave != 0) return;
-    int n_valid = 0;
-    for (int c = lane; c < k; c += 64) n_valid += ord[c] != kNoOrd;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) n_valid += armi::xor_stride(n_valid, off);
-    const double iq = inv_q[qg];
-    for (int c = lane; c < k; c += 64) {
-      const size_t o = (size_t)qg * k + c;
-      const bool v = ord[c] != kNoOrd;
-      out_scores[o] = v ? (float)(key[c] * iq) : kNegInf;
-      out_ids[o] = v ? ord[c] : -1;
-      out_rank[o] = v ? key[c] : kNegInfD;
-    }
-    if (lane == 0) {
-      out_count[qg] = n_valid;
-      flags[qg] = ARMI_FLAG_FALLBACK;
-    }
+    armi::write_top_k(key, ord, qg, k, armi::ScoreTimes{inv_q[qg]}, out_scores, out_ids, out_rank,
+                      out_count);
+    if (tid == 0) flags[qg] = ARMI_FLAG_FALLBACK;
   };
   if (bid < nq) {  // the query's own workgroup
     const int qg = bid;
@@ -2229,35 +2230,28 @@ __global__ __launch_bounds__(256) void dense_exact_scan_kernel(
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = armi::wave_id();
-  for (int e = tid; e < 2 * cap; e += 256) {
-    key[e] = kNegInfD;
-    ord[e] = kNoOrd;
-  }
   int32_t qf[DIM / 64];
   load_fixed<DIM>(queries + (size_t)q * DIM, lane, qf);
   const int64_t lo = (int64_t)blockIdx.x * rows_per_block;
   const int64_t hi = min(lo + rows_per_block, n_rows);
-  __syncthreads();
-  for (int64_t c0 = lo; c0 < hi; c0 += cap) {
-    for (int i = wave; i < cap; i += 4) {
-      const int64_t row = c0 + i;
+  // one row per wave and step, cap rows per round of the merge
+  armi::merge_stream(key, ord, cap, cap, hi - lo, [&](int64_t t0, int m, double* ck, int64_t* co) {
+    for (int i = wave; i < m; i += 4) {
+      const int64_t row = lo + t0 + i;
       double kk = kNegInfD;
       int64_t oo = kNoOrd;
-      if (row < hi) {
-        const bool on = (!row_mask || ((row_mask[row >> 6] >> (row & 63)) & 1ull)) && norm2[row] >= 0;
-        if (on) {
-          const int64_t dot = wave_dot_exact<DIM>(qf, rows + (size_t)row * DIM, lane);
-          kk = (double)dot * inv_norm[row];
-          oo = ordinal_base + row;
-        }
+      const bool on = (!row_mask || ((row_mask[row >> 6] >> (row & 63)) & 1ull)) && norm2[row] >= 0;
+      if (on) {
+        const int64_t dot = wave_dot_exact<DIM>(qf, rows + (size_t)row * DIM, lane);
+        kk = (double)dot * inv_norm[row];
+        oo = ordinal_base + row;
       }
       if (lane == 0) {
-        key[cap + i] = kk;
-        ord[cap + i] = oo;
+        ck[i] = kk;
+        co[i] = oo;
       }
     }
-    armi::lds_sort_rank_desc(key, ord, 2 * cap);
-  }
+  });
   const size_t base = ((size_t)q * gridDim.x + blockIdx.x) * cap;
   for (int e = tid; e < cap; e += 256) {
     ex_key[base + e] = key[e];
@@ -2941,12 +2935,6 @@ __global__ __launch_bounds__(kDenseMergeThreads) void dense_tail_finish_kernel(
   const int wave = armi::wave_id();
   int32_t qf[DIM / 64];
   load_fixed<DIM>(queries + (size_t)qg * DIM, lane, qf);
-  int64_t n2q = 0;
-#pragma unroll
-  for (int i = 0; i < DIM / 64; ++i) n2q += (int64_t)qf[i] * (int64_t)qf[i];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) n2q += armi::xor_stride(n2q, off);
-  const double iq = n2q > 0 ? 1.0 / sqrt((double)n2q) : 0.0;
   // gather the workgroup lists (64 workgroups at a time) into s_list, in workgroup order
   int base = 0;  // survivors before this chunk (uniform)
   for (int w0 = 0; w0 < n_wg; w0 += 64) {
@@ -2973,17 +2961,18 @@ __global__ __launch_bounds__(kDenseMergeThreads) void dense_tail_finish_kernel(
     base = *s_total;
     __syncthreads();
   }
+  // (1 / |q| from here, not from the top: it is not live across the gather)
+  const double iq = inv_sqrt_norm2(query_norm2<DIM>(qf));
   const int cnt = base;
   const bool overflow = cnt > kTailCap;  // workgroup-uniform
   // the tail's candidates in [0, p): the survivors' exact keys (eight rows per wave and round), or
   // after an overflow the best of every row
   int p;
   if (!overflow) {
+    // (the scoring loop stays in this kernel, storing only rows that rank over a filled list:
+    // through store_keys8 the kernel needs 8 to 30 more VGPRs and loses an occupancy bracket)
     p = max(8, armi::pow2_at_least(cnt > k ? cnt : k));
-    for (int e = tid; e < p; e += kDenseMergeThreads) {
-      key[e] = kNegInfD;
-      ord[e] = kNoOrd;
-    }
+    armi::fill_empty(key, ord, 0, p);
     __syncthreads();
     for (int b = 8 * wave; b < cnt; b += 8 * (kDenseMergeThreads / 64)) {
       int32_t rr[8];
@@ -2999,9 +2988,12 @@ __global__ __launch_bounds__(kDenseMergeThreads) void dense_tail_finish_kernel(
       }
     }
   } else {
+    // More than kTailCap survivors means more than kTailCap rows, so the rows take the chunked
+    // path of collect_top_rows, which leaves the best kColChunk of them in front.
+    static_assert(kTailCap >= kColChunk, "an overflowed tail is longer than one collect chunk");
     collect_top_rows<DIM>(nullptr, 0, n_rows, k, qf, rows, inv_norm, norm2, row_mask, ordinal_base,
                           key, ord);
-    p = n_rows <= kColChunk ? armi::pow2_at_least((int)n_rows > k ? (int)n_rows : k) : kColChunk;
+    p = kColChunk;
   }
   // the main list behind them (p >= k), then one sort of both
   const int main_n = min(max(main_count[qg], 0), k);
@@ -3012,22 +3004,9 @@ __global__ __launch_bounds__(kDenseMergeThreads) void dense_tail_finish_kernel(
     ord[e] = v ? main_ids[(size_t)qg * k + c] : kNoOrd;
   }
   armi::lds_sort_rank_desc(key, ord, 2 * p);
-  if (wave != 0) return;
-  int n_valid = 0;
-  for (int c = lane; c < k; c += 64) n_valid += ord[c] != kNoOrd;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) n_valid += armi::xor_stride(n_valid, off);
-  for (int c = lane; c < k; c += 64) {
-    const size_t o = (size_t)qg * k + c;
-    const bool v = ord[c] != kNoOrd;
-    out_scores[o] = v ? (float)(key[c] * iq) : kNegInf;
-    out_ids[o] = v ? ord[c] : -1;
-    if (out_rank) out_rank[o] = v ? key[c] : kNegInfD;
-  }
-  if (lane == 0) {
-    out_count[qg] = n_valid;
-    out_flags[qg] = overflow ? ARMI_FLAG_FALLBACK : ARMI_FLAG_CERTIFIED;
-  }
+  armi::write_top_k(key, ord, qg, k, armi::ScoreTimes{iq}, out_scores, out_ids, out_rank,
+                    out_count);
+  if (tid == 0) out_flags[qg] = overflow ? ARMI_FLAG_FALLBACK : ARMI_FLAG_CERTIFIED;
 }
 
 // ARMI_TAIL_PASS=general forces armi_dense_tail_topk's general path (armi_dense_topk over the tail,
@@ -3083,45 +3062,8 @@ TailWorkspace carve_tail(void* base, const armi_index* tail, int nq, int k) {
 // sorts them and keeps the chunk's top k. A call whose longest list fits one chunk writes the
 // outputs from that workgroup (`direct`); otherwise the chunk lists go to the workspace
 // ([query][chunk][k]) and dense_rowlist_merge_kernel, one workgroup per query, merges them.
-constexpr int kRowlistChunk = kColChunk;
+using armi::kRowlistChunk;
 constexpr size_t kRowlistLds = 2 * kRowlistChunk * 16;
-
-// The top k of key / ord (sorted) as the call's outputs for query qg, by wave 0.
-__device__ __forceinline__ void rowlist_write_out(const double* key, const int64_t* ord, int qg,
-                                                  int k, double iq, float* __restrict__ out_scores,
-                                                  int64_t* __restrict__ out_ids,
-                                                  double* __restrict__ out_rank,
-                                                  int32_t* __restrict__ out_count,
-                                                  uint32_t* __restrict__ out_flags) {
-  const int lane = threadIdx.x & 63;
-  if (armi::wave_id() != 0) return;
-  int n_valid = 0;
-  for (int c = lane; c < k; c += 64) n_valid += ord[c] != kNoOrd;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) n_valid += armi::xor_stride(n_valid, off);
-  for (int c = lane; c < k; c += 64) {
-    const size_t o = (size_t)qg * k + c;
-    const bool v = ord[c] != kNoOrd;
-    out_scores[o] = v ? (float)(key[c] * iq) : kNegInf;
-    out_ids[o] = v ? ord[c] : -1;
-    if (out_rank) out_rank[o] = v ? key[c] : kNegInfD;
-  }
-  if (lane == 0) {
-    out_count[qg] = n_valid;
-    out_flags[qg] = ARMI_FLAG_ROWLIST;
-  }
-}
-
-// 1 / |q| of the 2^24-scaled query, the merge kernels' arithmetic (query_norms_kernel).
-template <int DIM>
-__device__ __forceinline__ double rowlist_inv_q(const int32_t (&qf)[DIM / 64]) {
-  int64_t n2q = 0;
-#pragma unroll
-  for (int i = 0; i < DIM / 64; ++i) n2q += (int64_t)qf[i] * (int64_t)qf[i];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) n2q += armi::xor_stride(n2q, off);
-  return n2q > 0 ? 1.0 / sqrt((double)n2q) : 0.0;
-}
 
 template <int DIM>
 __global__ __launch_bounds__(kDenseMergeThreads) void dense_rowlist_chunk_kernel(
@@ -3140,19 +3082,18 @@ __global__ __launch_bounds__(kDenseMergeThreads) void dense_rowlist_chunk_kernel
   const int chunk = blockIdx.x;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-  const int wave = armi::wave_id();
-  const int l = q_list[qg];
-  const bool listed = l >= 0 && l < n_lists;  // a query naming no list ranks nothing
-  const int64_t lo = listed ? list_ptr[l] : 0;
-  const int64_t len = listed ? min<int64_t>(list_ptr[l + 1] - lo, max_list_rows) : 0;
+  const armi::RowSpan span = armi::rowlist_span(list_ptr, q_list, n_lists, max_list_rows, qg);
   const int64_t c0 = (int64_t)chunk * kRowlistChunk;
   // past the list's end (workgroup-uniform); an empty list's answer comes from chunk 0 (direct)
   // or from the merge kernel
-  if (c0 >= len && !(direct && chunk == 0)) return;
-  const int m = (int)max<int64_t>(0, min<int64_t>(kRowlistChunk, len - c0));
+  if (c0 >= span.len && !(direct && chunk == 0)) return;
+  const int m = (int)max<int64_t>(0, min<int64_t>(kRowlistChunk, span.len - c0));
   int32_t qf[DIM / 64];
   load_fixed<DIM>(queries + (size_t)qg * DIM, lane, qf);
+  // (the scoring loop stays in this kernel, every slot of the chunk stored by it: through
+  // score_chunk / store_keys8 the kernel loses an occupancy bracket at three of the four dims)
   constexpr int kPerWave = kRowlistChunk / (kDenseMergeThreads / 64);  // 64 entries per wave
+  const int wave = armi::wave_id();
   for (int b = 0; b < kPerWave; b += 8) {
     const int e0 = kPerWave * wave + b;
     double kk = kNegInfD;
@@ -3163,7 +3104,7 @@ __global__ __launch_bounds__(kDenseMergeThreads) void dense_rowlist_chunk_kernel
       for (int j = 0; j < 8; ++j) {
         int32_t o = -1;
         if (e0 + j < m) {
-          const int32_t r = list_rows[lo + c0 + e0 + j];
+          const int32_t r = list_rows[span.lo + c0 + e0 + j];
           // rows outside the index or outside the fp16 domain never rank
           if (r >= 0 && r < n_rows && norm2[r] >= 0) o = r;
         }
@@ -3179,8 +3120,9 @@ __global__ __launch_bounds__(kDenseMergeThreads) void dense_rowlist_chunk_kernel
   }
   armi::lds_sort_rank_desc(key, ord, armi::pow2_at_least(m > k ? m : k));
   if (direct) {
-    rowlist_write_out(key, ord, qg, k, rowlist_inv_q<DIM>(qf), out_scores, out_ids, out_rank,
-                      out_count, out_flags);
+    armi::write_top_k(key, ord, qg, k, armi::ScoreTimes{inv_sqrt_norm2(query_norm2<DIM>(qf))},
+                      out_scores, out_ids, out_rank, out_count);
+    if (tid == 0) out_flags[qg] = ARMI_FLAG_ROWLIST;
     return;
   }
   const size_t base = ((size_t)qg * gridDim.x + chunk) * k;
@@ -3190,9 +3132,8 @@ __global__ __launch_bounds__(kDenseMergeThreads) void dense_rowlist_chunk_kernel
   }
 }
 
-// One workgroup per query: the chunk lists of its row list (ceil(len / kRowlistChunk) lists of k
-// sorted entries, empty slots ordinal kNoOrd) through LDS, [0, kRowlistChunk) the best so far,
-// [kRowlistChunk, 2 kRowlistChunk) the next entries, one bitonic sort per round.
+// One workgroup per query: the chunk lists of its row list (armi::rowlist_chunks(len) lists of k
+// sorted entries, empty slots the empty entry) streamed through armi::merge_stream.
 template <int DIM>
 __global__ __launch_bounds__(kDenseMergeThreads) void dense_rowlist_merge_kernel(
     const double* __restrict__ part_key, const int64_t* __restrict__ part_ord, int chunks_max,
@@ -3206,37 +3147,23 @@ __global__ __launch_bounds__(kDenseMergeThreads) void dense_rowlist_merge_kernel
   int64_t* ord = reinterpret_cast<int64_t*>(smem + 2 * kRowlistChunk * 8);    // [2 * kRowlistChunk]
   const int qg = blockIdx.x;
   const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int l = q_list[qg];
-  const int64_t len =
-      l >= 0 && l < n_lists ? min<int64_t>(list_ptr[l + 1] - list_ptr[l], max_list_rows) : 0;
-  const int64_t chunks =
-      min<int64_t>(chunks_max, (max<int64_t>(len, 0) + kRowlistChunk - 1) / kRowlistChunk);
-  const int64_t total = chunks * k;  // entries [0, total) of the query's chunk lists
+  const int64_t len = armi::rowlist_span(list_ptr, q_list, n_lists, max_list_rows, qg).len;
+  const int64_t chunks = min<int64_t>(chunks_max, armi::rowlist_chunks(len));
   const double* pk = part_key + (size_t)qg * chunks_max * k;
   const int64_t* po = part_ord + (size_t)qg * chunks_max * k;
-  for (int e = tid; e < 2 * kRowlistChunk; e += kDenseMergeThreads) {
-    key[e] = kNegInfD;
-    ord[e] = kNoOrd;
-  }
-  for (int64_t t0 = 0; t0 < total; t0 += kRowlistChunk) {
-    __syncthreads();  // the previous sort is done with [kRowlistChunk, 2 kRowlistChunk)
-    for (int e = tid; e < kRowlistChunk; e += kDenseMergeThreads) {
-      const bool v = t0 + e < total;
-      key[kRowlistChunk + e] = v ? pk[t0 + e] : kNegInfD;
-      ord[kRowlistChunk + e] = v ? po[t0 + e] : kNoOrd;
-    }
-    armi::lds_sort_rank_desc(key, ord, 2 * kRowlistChunk);
-  }
-  __syncthreads();
+  // entries [0, chunks * k) of the query's chunk lists
+  armi::merge_stream(key, ord, kRowlistChunk, k, chunks * k,
+                     [&](int64_t t0, int m, double* ck, int64_t* co) {
+                       for (int e = tid; e < m; e += kDenseMergeThreads) {
+                         ck[e] = pk[t0 + e];
+                         co[e] = po[t0 + e];
+                       }
+                     });
   int32_t qf[DIM / 64];
-  load_fixed<DIM>(queries + (size_t)qg * DIM, lane, qf);
-  rowlist_write_out(key, ord, qg, k, rowlist_inv_q<DIM>(qf), out_scores, out_ids, out_rank,
-                    out_count, out_flags);
-}
-
-int rowlist_chunks(int64_t max_list_rows) {
-  return (int)std::max<int64_t>(1, (max_list_rows + kRowlistChunk - 1) / kRowlistChunk);
+  load_fixed<DIM>(queries + (size_t)qg * DIM, tid & 63, qf);
+  armi::write_top_k(key, ord, qg, k, armi::ScoreTimes{inv_sqrt_norm2(query_norm2<DIM>(qf))},
+                    out_scores, out_ids, out_rank, out_count);
+  if (tid == 0) out_flags[qg] = ARMI_FLAG_ROWLIST;
 }
 
 template <typename F>
@@ -3412,7 +3339,7 @@ size_t armi_dense_rowlist_workspace_bytes(const armi_index* idx, int n_queries, 
                                           int64_t max_list_rows) {
   if (!idx || n_queries <= 0 || k <= 0 || max_list_rows < 0) return 0;
   k = std::min(k, kMaxK);
-  const int chunks = rowlist_chunks(max_list_rows);
+  const int chunks = armi::rowlist_grid_chunks(max_list_rows);
   if (chunks == 1) return 256;  // one chunk per list: the chunk workgroups write the outputs
   return 2 * armi::align_up((size_t)n_queries * chunks * k * 8, 256) + 256;
 }
@@ -3440,7 +3367,7 @@ int armi_dense_rowlist_topk(const armi_index* idx, const uint16_t* queries, int 
                "armi_dense_rowlist_topk: workspace too small");
   ARMI_HIP(hipSetDevice(idx->device));
   const int nq = n_queries;
-  const int chunks = rowlist_chunks(max_list_rows);
+  const int chunks = armi::rowlist_grid_chunks(max_list_rows);
   const int direct = chunks == 1;
   armi::Carver cv(workspace);
   double* part_key = cv.take<double>(direct ? 0 : (size_t)nq * chunks * k);

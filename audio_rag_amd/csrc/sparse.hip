@@ -37,8 +37,13 @@
 #include <vector>
 
 #include "armi_index.h"
+#include "armi_rank_list.h"
 
 namespace {
+
+using armi::kNegInfD;
+using armi::kNoOrd;
+using armi::kRowlistChunk;
 
 constexpr int kQB = 64;                 // queries per pass
 constexpr int kQW = 4;                  // queries per wave
@@ -1868,36 +1873,13 @@ __global__ __launch_bounds__(kUnpackThreads) void query_slots_unpack_kernel(
 // ------------------------------------------------------------------------ row-list top-k
 // armi_sparse_rowlist_topk: the exact ranking of given rows (a selective metadata filter's matches)
 // from the forward CSR, without the inverted index. Grid (chunks, queries): workgroup (c, q)
-// scores rows [c * kRlChunk, ...) of query q's list, one row per thread and round, by the merge
-// join of the row's and the query's ascending term ids (the products rounded, then added in that
-// order: the exact scan's and the oracle's arithmetic), sorts the rows that share a term and keeps
-// the chunk's top k. A call whose longest list fits one chunk writes the outputs from that
+// scores rows [c * kRowlistChunk, ...) of query q's list, one row per thread and round, by the
+// merge join of the row's and the query's ascending term ids (the products rounded, then added in
+// that order: the exact scan's and the oracle's arithmetic), sorts the rows that share a term and
+// keeps the chunk's top k. A call whose longest list fits one chunk writes the outputs from that
 // workgroup (`direct`); otherwise the chunk lists go to the workspace ([query][chunk][k]) and
 // sparse_rowlist_merge_kernel, one workgroup per query, merges them.
-constexpr int kRlChunk = 512;
 constexpr int kRlThreads = 256;
-constexpr double kRlNegInf = -std::numeric_limits<double>::infinity();
-constexpr int64_t kRlNoOrd = std::numeric_limits<int64_t>::max();
-
-// The top k of key / ord (sorted) as the call's outputs for query q (k <= kRlThreads).
-__device__ __forceinline__ void rowlist_write_out(const double* key, const int64_t* ord, int q,
-                                                  int k, float* __restrict__ out_scores,
-                                                  int64_t* __restrict__ out_ids,
-                                                  int32_t* __restrict__ out_count,
-                                                  uint32_t* __restrict__ out_flags) {
-  const int tid = threadIdx.x;
-  const bool v = tid < k && ord[tid] != kRlNoOrd;
-  const int n_valid = __syncthreads_count(v);
-  if (tid < k) {
-    const size_t o = (size_t)q * k + tid;
-    out_scores[o] = v ? (float)key[tid] : kNegInf;
-    out_ids[o] = v ? ord[tid] : -1;
-  }
-  if (tid == 0) {
-    out_count[q] = n_valid;
-    out_flags[q] = ARMI_FLAG_ROWLIST;
-  }
-}
 
 __global__ __launch_bounds__(kRlThreads) void sparse_rowlist_chunk_kernel(
     const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
@@ -1909,26 +1891,23 @@ __global__ __launch_bounds__(kRlThreads) void sparse_rowlist_chunk_kernel(
     double* __restrict__ part_key, int64_t* __restrict__ part_ord, float* __restrict__ out_scores,
     int64_t* __restrict__ out_ids, int32_t* __restrict__ out_count,
     uint32_t* __restrict__ out_flags) {
-  __shared__ double key[kRlChunk];
-  __shared__ int64_t ord[kRlChunk];
+  __shared__ double key[kRowlistChunk];
+  __shared__ int64_t ord[kRowlistChunk];
   const int q = blockIdx.y;
   const int chunk = blockIdx.x;
   const int tid = threadIdx.x;
-  const int l = q_list[q];
-  const bool listed = l >= 0 && l < n_lists;  // a query naming no list ranks nothing
-  const int64_t lo = listed ? list_ptr[l] : 0;
-  const int64_t len = listed ? min<int64_t>(list_ptr[l + 1] - lo, max_list_rows) : 0;
-  const int64_t c0 = (int64_t)chunk * kRlChunk;
+  const armi::RowSpan span = armi::rowlist_span(list_ptr, q_list, n_lists, max_list_rows, q);
+  const int64_t c0 = (int64_t)chunk * kRowlistChunk;
   // past the list's end (workgroup-uniform); an empty list's answer comes from chunk 0 (direct)
   // or from the merge kernel
-  if (c0 >= len && !(direct && chunk == 0)) return;
-  const int m = (int)max<int64_t>(0, min<int64_t>(kRlChunk, len - c0));
+  if (c0 >= span.len && !(direct && chunk == 0)) return;
+  const int m = (int)max<int64_t>(0, min<int64_t>(kRowlistChunk, span.len - c0));
   const int32_t qa = q_indptr[q], qb = q_indptr[q + 1];
-  for (int e = tid; e < kRlChunk; e += kRlThreads) {
-    double kk = kRlNegInf;
-    int64_t oo = kRlNoOrd;
-    if (e < m) {
-      const int32_t r = list_rows[lo + c0 + e];
+  armi::rank_chunk(key, ord, m, k, [&](int64_t, int, double* ck, int64_t* co) {
+    for (int e = tid; e < m; e += kRlThreads) {
+      double kk = kNegInfD;
+      int64_t oo = kNoOrd;
+      const int32_t r = list_rows[span.lo + c0 + e];
       if (r >= 0 && r < n_rows) {
         int64_t i = indptr[r];
         const int64_t ie = indptr[r + 1];
@@ -1949,13 +1928,13 @@ __global__ __launch_bounds__(kRlThreads) void sparse_rowlist_chunk_kernel(
           oo = ordinal_base + r;
         }
       }
+      ck[e] = kk;
+      co[e] = oo;
     }
-    key[e] = kk;
-    ord[e] = oo;
-  }
-  armi::lds_sort_rank_desc(key, ord, armi::pow2_at_least(m > k ? m : k));
+  });
   if (direct) {
-    rowlist_write_out(key, ord, q, k, out_scores, out_ids, out_count, out_flags);
+    armi::write_top_k(key, ord, q, k, armi::ScoreIsKey{}, out_scores, out_ids, nullptr, out_count);
+    if (tid == 0) out_flags[q] = ARMI_FLAG_ROWLIST;
     return;
   }
   const size_t base = ((size_t)q * gridDim.x + chunk) * k;
@@ -1965,44 +1944,30 @@ __global__ __launch_bounds__(kRlThreads) void sparse_rowlist_chunk_kernel(
   }
 }
 
-// One workgroup per query: the chunk lists of its row list through LDS, [0, kRlChunk) the best so
-// far, [kRlChunk, 2 kRlChunk) the next entries, one bitonic sort per round.
+// One workgroup per query: the chunk lists of its row list streamed through armi::merge_stream.
 __global__ __launch_bounds__(kRlThreads) void sparse_rowlist_merge_kernel(
     const double* __restrict__ part_key, const int64_t* __restrict__ part_ord, int chunks_max,
     int k, const int64_t* __restrict__ list_ptr, const int32_t* __restrict__ q_list,
     int n_lists, int64_t max_list_rows, float* __restrict__ out_scores,
     int64_t* __restrict__ out_ids, int32_t* __restrict__ out_count,
     uint32_t* __restrict__ out_flags) {
-  __shared__ double key[2 * kRlChunk];
-  __shared__ int64_t ord[2 * kRlChunk];
+  __shared__ double key[2 * kRowlistChunk];
+  __shared__ int64_t ord[2 * kRowlistChunk];
   const int q = blockIdx.x;
   const int tid = threadIdx.x;
-  const int l = q_list[q];
-  const int64_t len =
-      l >= 0 && l < n_lists ? min<int64_t>(list_ptr[l + 1] - list_ptr[l], max_list_rows) : 0;
-  const int64_t chunks = min<int64_t>(chunks_max, (max<int64_t>(len, 0) + kRlChunk - 1) / kRlChunk);
-  const int64_t total = chunks * k;
+  const int64_t len = armi::rowlist_span(list_ptr, q_list, n_lists, max_list_rows, q).len;
+  const int64_t chunks = min<int64_t>(chunks_max, armi::rowlist_chunks(len));
   const double* pk = part_key + (size_t)q * chunks_max * k;
   const int64_t* po = part_ord + (size_t)q * chunks_max * k;
-  for (int e = tid; e < 2 * kRlChunk; e += kRlThreads) {
-    key[e] = kRlNegInf;
-    ord[e] = kRlNoOrd;
-  }
-  for (int64_t t0 = 0; t0 < total; t0 += kRlChunk) {
-    __syncthreads();  // the previous sort is done with [kRlChunk, 2 kRlChunk)
-    for (int e = tid; e < kRlChunk; e += kRlThreads) {
-      const bool v = t0 + e < total;
-      key[kRlChunk + e] = v ? pk[t0 + e] : kRlNegInf;
-      ord[kRlChunk + e] = v ? po[t0 + e] : kRlNoOrd;
-    }
-    armi::lds_sort_rank_desc(key, ord, 2 * kRlChunk);
-  }
-  __syncthreads();
-  rowlist_write_out(key, ord, q, k, out_scores, out_ids, out_count, out_flags);
-}
-
-int rowlist_chunks(int64_t max_list_rows) {
-  return (int)std::max<int64_t>(1, (max_list_rows + kRlChunk - 1) / kRlChunk);
+  armi::merge_stream(key, ord, kRowlistChunk, k, chunks * k,
+                     [&](int64_t t0, int m, double* ck, int64_t* co) {
+                       for (int e = tid; e < m; e += kRlThreads) {
+                         ck[e] = pk[t0 + e];
+                         co[e] = po[t0 + e];
+                       }
+                     });
+  armi::write_top_k(key, ord, q, k, armi::ScoreIsKey{}, out_scores, out_ids, nullptr, out_count);
+  if (tid == 0) out_flags[q] = ARMI_FLAG_ROWLIST;
 }
 
 // ------------------------------------------------------------------------ sparse tail pass
@@ -2040,27 +2005,6 @@ constexpr int kStGroup = 256;     // chunk counts scanned together by the finish
 static_assert(kStRowsPerWave % kStBatch == 0, "whole batches per wave");
 static_assert(kStChunk + kMaxK <= kStSort && kStChunk <= kStThreads, "direct finish buffer");
 
-// Sorted key / ord [0, k) as query q's outputs (k <= blockDim.x); flags pass through.
-__device__ __forceinline__ void tail_write_out(const double* key, const int64_t* ord, int q, int k,
-                                               const uint32_t* __restrict__ main_flags,
-                                               float* __restrict__ out_scores,
-                                               int64_t* __restrict__ out_ids,
-                                               int32_t* __restrict__ out_count,
-                                               uint32_t* __restrict__ out_flags) {
-  const int tid = threadIdx.x;
-  const bool v = tid < k && ord[tid] != kRlNoOrd;
-  const int n_valid = __syncthreads_count(v);
-  if (tid < k) {
-    const size_t o = (size_t)q * k + tid;
-    out_scores[o] = v ? (float)key[tid] : kNegInf;
-    out_ids[o] = v ? ord[tid] : -1;
-  }
-  if (tid == 0) {
-    out_count[q] = n_valid;
-    if (out_flags) out_flags[q] = main_flags ? main_flags[q] : 0u;
-  }
-}
-
 // x, the same in every lane, as a scalar (loop bounds and branches on it stay scalar).
 __device__ __forceinline__ int64_t tail_uniform(int64_t x) {
   const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)x);
@@ -2087,8 +2031,8 @@ __device__ __forceinline__ void tail_load_main(double* key, int64_t* ord,
   const int mc = min(max(main_count[q], 0), k);
   for (int e = threadIdx.x; e < k; e += blockDim.x) {
     const bool v = e < mc;
-    key[e] = v ? (double)main_scores[(size_t)q * k + e] : kRlNegInf;
-    ord[e] = v ? main_ids[(size_t)q * k + e] : kRlNoOrd;
+    key[e] = v ? (double)main_scores[(size_t)q * k + e] : kNegInfD;
+    ord[e] = v ? main_ids[(size_t)q * k + e] : kNoOrd;
   }
 }
 
@@ -2216,16 +2160,14 @@ __global__ __launch_bounds__(kStThreads) void sparse_tail_scan_kernel(
   }
   if (direct || cnt > kc) {
     const int n = armi::pow2_at_least(max(base + cnt, 2));
-    for (int e = base + cnt + tid; e < n; e += kStThreads) {
-      key[e] = kRlNegInf;
-      ord[e] = kRlNoOrd;
-    }
+    armi::fill_empty(key, ord, base + cnt, n);
     armi::lds_sort_rank_desc(key, ord, n);
   } else {
     __syncthreads();
   }
   if (direct) {
-    tail_write_out(key, ord, q, k, main_flags, out_scores, out_ids, out_count, out_flags);
+    armi::write_top_k(key, ord, q, k, armi::ScoreIsKey{}, out_scores, out_ids, nullptr, out_count);
+    if (tid == 0 && out_flags) out_flags[q] = main_flags ? main_flags[q] : 0u;  // pass through
     return;
   }
   cnt = min(cnt, kc);
@@ -2300,15 +2242,13 @@ __global__ __launch_bounds__(kStThreads) void sparse_tail_finish_kernel(
   }
   if (fill > 0) {  // (fill == 0: [0, k) is sorted, by the last round or as the main list came)
     const int n = armi::pow2_at_least(k + fill);
-    for (int e = k + fill + tid; e < n; e += kStThreads) {
-      key[e] = kRlNegInf;
-      ord[e] = kRlNoOrd;
-    }
+    armi::fill_empty(key, ord, k + fill, n);
     armi::lds_sort_rank_desc(key, ord, n);
   } else {
     __syncthreads();
   }
-  tail_write_out(key, ord, q, k, main_flags, out_scores, out_ids, out_count, out_flags);
+  armi::write_top_k(key, ord, q, k, armi::ScoreIsKey{}, out_scores, out_ids, nullptr, out_count);
+  if (tid == 0 && out_flags) out_flags[q] = main_flags ? main_flags[q] : 0u;  // pass through
 }
 
 int64_t tail_chunks(int64_t tail_rows) { return (tail_rows + kStChunk - 1) / kStChunk; }
@@ -2320,7 +2260,7 @@ extern "C" {
 size_t armi_sparse_rowlist_workspace_bytes(int n_queries, int k, int64_t max_list_rows) {
   if (n_queries <= 0 || k <= 0 || max_list_rows < 0) return 0;
   k = std::min(k, kMaxK);
-  const int chunks = rowlist_chunks(max_list_rows);
+  const int chunks = armi::rowlist_grid_chunks(max_list_rows);
   if (chunks == 1) return 256;  // one chunk per list: the chunk workgroups write the outputs
   return 2 * armi::align_up((size_t)n_queries * chunks * k * 8, 256) + 256;
 }
@@ -2349,7 +2289,7 @@ int armi_sparse_rowlist_topk(const int64_t* indptr, const int32_t* indices, cons
                "armi_sparse_rowlist_topk: null pointer argument");
   ARMI_REQUIRE(workspace_bytes >= armi_sparse_rowlist_workspace_bytes(n_queries, k, max_list_rows),
                "armi_sparse_rowlist_topk: workspace too small");
-  const int chunks = rowlist_chunks(max_list_rows);
+  const int chunks = armi::rowlist_grid_chunks(max_list_rows);
   const int direct = chunks == 1;
   armi::Carver cv(workspace);
   double* part_key = cv.take<double>(direct ? 0 : (size_t)n_queries * chunks * k);

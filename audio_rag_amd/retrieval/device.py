@@ -62,6 +62,37 @@ class TopK:
         return tuple(t for t in (self._scores, self.ids, self._rank, self.count, self.flags)
                      if t is not None)
 
+    @classmethod
+    def empty(cls, b: int, k: int, device: torch.device, rank: bool, flags: bool = True) -> "TopK":
+        """Uninitialised outputs of a call over b queries: scores, ids, count, and rank / flags
+        when the call writes them."""
+        def new(shape, dtype):
+            return torch.empty(shape, dtype=dtype, device=device)
+
+        return cls(scores=new((b, k), torch.float32), ids=new((b, k), torch.int64),
+                   rank=new((b, k), torch.float64) if rank else None, count=new(b, torch.int32),
+                   flags=new(b, torch.int32) if flags else None)
+
+
+def _check_k(k: int) -> None:
+    if not 1 <= k <= MAX_K:
+        raise ValueError(f"k must be in [1, {MAX_K}]")
+
+
+def _check_query_csr(q_indptr: torch.Tensor, q_indices: torch.Tensor,
+                     q_values: torch.Tensor) -> None:
+    for t, dt, name in ((q_indptr, torch.int32, "q_indptr"), (q_indices, torch.int32, "q_indices"),
+                        (q_values, torch.float32, "q_values")):
+        if t.dtype != dt or t.dim() != 1 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous 1-D {dt} device tensor")
+
+
+def _workspace(workspace: torch.Tensor | None, need: int, device: torch.device) -> torch.Tensor:
+    """The caller's workspace when it holds `need` bytes, else a fresh one."""
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+    return workspace
+
 
 def _check_row_lists(list_ptr: torch.Tensor, list_rows: torch.Tensor, q_list: torch.Tensor,
                      n_queries: int, max_list_rows: int, n_rows: int,
@@ -173,8 +204,7 @@ class DenseIndex:
         """Cosine top-k of every query row. row_mask: int64 tensor holding a bitmask of enabled
         rows (bit r of word r // 64), or None."""
         _check_fp16_2d(queries, "queries", self.dim)
-        if not 1 <= k <= MAX_K:
-            raise ValueError(f"k must be in [1, {MAX_K}]")
+        _check_k(k)
         b = int(queries.shape[0])
         dev = self.device
         if row_mask is not None:
@@ -182,14 +212,8 @@ class DenseIndex:
             if row_mask.dtype != torch.int64 or row_mask.numel() < need or not row_mask.is_cuda:
                 raise ValueError(f"row_mask must be an int64 device tensor of >= {need} words")
         if out is None:
-            out = TopK(scores=torch.empty((b, k), dtype=torch.float32, device=dev),
-                       ids=torch.empty((b, k), dtype=torch.int64, device=dev),
-                       rank=torch.empty((b, k), dtype=torch.float64, device=dev),
-                       count=torch.empty(b, dtype=torch.int32, device=dev),
-                       flags=torch.empty(b, dtype=torch.int32, device=dev))
-        need = self.workspace_bytes(max(b, 1), k, exact)
-        if workspace is None or workspace.numel() < need:
-            workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+            out = TopK.empty(b, k, dev, rank=True)
+        workspace = _workspace(workspace, self.workspace_bytes(max(b, 1), k, exact), dev)
         s = stream_handle()
         if exact:
             call("armi_dense_exact_topk", self._handle, ptr(queries), b, k, ptr(row_mask),
@@ -217,24 +241,17 @@ class DenseIndex:
         (they are uploaded); the same ranking, scores and rank keys as topk(row_mask=...), flags
         ARMI_FLAG_ROWLIST."""
         _check_fp16_2d(queries, "queries", self.dim)
-        if not 1 <= k <= MAX_K:
-            raise ValueError(f"k must be in [1, {MAX_K}]")
+        _check_k(k)
         b = int(queries.shape[0])
         dev = self.device
         n_lists = _check_row_lists(list_ptr, list_rows, q_list, b, int(max_list_rows),
                                    self.n_rows, dev)
         list_ptr, list_rows, q_list = (_on_device(t, dev) for t in (list_ptr, list_rows, q_list))
         if out is None:
-            out = TopK(scores=torch.empty((b, k), dtype=torch.float32, device=dev),
-                       ids=torch.empty((b, k), dtype=torch.int64, device=dev),
-                       rank=torch.empty((b, k), dtype=torch.float64, device=dev),
-                       count=torch.empty(b, dtype=torch.int32, device=dev),
-                       flags=torch.empty(b, dtype=torch.int32, device=dev))
+            out = TopK.empty(b, k, dev, rank=True)
         if b == 0:
             return out
-        need = self.rowlist_workspace_bytes(b, k, max_list_rows)
-        if workspace is None or workspace.numel() < need:
-            workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        workspace = _workspace(workspace, self.rowlist_workspace_bytes(b, k, max_list_rows), dev)
         call("armi_dense_rowlist_topk", self._handle, ptr(queries), b, k, ptr(list_ptr),
              ptr(list_rows), ptr(q_list), n_lists, int(max_list_rows), ptr(out.scores),
              ptr(out.ids), ptr(out.rank), ptr(out.count), ptr(out.flags), ptr(workspace),
@@ -285,8 +302,7 @@ class TailIndex(DenseIndex):
         """The top-k over the main index and this segment, from `main` = the main index's
         topk(queries, k) (armi_dense_tail_topk). row_mask: bit r = row r of this segment."""
         _check_fp16_2d(queries, "queries", self.dim)
-        if not 1 <= k <= MAX_K:
-            raise ValueError(f"k must be in [1, {MAX_K}]")
+        _check_k(k)
         b = int(queries.shape[0])
         if tuple(main.ids.shape) != (b, k):
             raise ValueError("main must be the main index's top-k of the same queries and k")
@@ -295,16 +311,10 @@ class TailIndex(DenseIndex):
             need = (self.n_rows + 63) // 64
             if row_mask.dtype != torch.int64 or row_mask.numel() < need or not row_mask.is_cuda:
                 raise ValueError(f"row_mask must be an int64 device tensor of >= {need} words")
-        out = TopK(scores=torch.empty((b, k), dtype=torch.float32, device=dev),
-                   ids=torch.empty((b, k), dtype=torch.int64, device=dev),
-                   rank=torch.empty((b, k), dtype=torch.float64, device=dev),
-                   count=torch.empty(b, dtype=torch.int32, device=dev),
-                   flags=torch.empty(b, dtype=torch.int32, device=dev))
+        out = TopK.empty(b, k, dev, rank=True)
         if b == 0:
             return out
-        need = self.tail_workspace_bytes(b, k)
-        if workspace is None or workspace.numel() < need:
-            workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        workspace = _workspace(workspace, self.tail_workspace_bytes(b, k), dev)
         m_scores, m_ids, m_rank, m_count = (t.contiguous() for t in
                                             (main.scores, main.ids, main.rank, main.count))
         call("armi_dense_tail_topk", self._handle, ptr(queries), b, k, ptr(row_mask), ptr(m_scores),
@@ -368,19 +378,13 @@ class SparseIndex:
              row_mask: torch.Tensor | None = None, workspace: torch.Tensor | None = None) -> TopK:
         """Sparse dot top-k for a query CSR (q_indptr int32 [B+1], ascending q_indices int32,
         q_values float32, all on the device)."""
-        if not 1 <= k <= MAX_K:
-            raise ValueError(f"k must be in [1, {MAX_K}]")
+        _check_k(k)
         b = int(q_indptr.numel()) - 1
         dev = self.device
-        out = TopK(scores=torch.empty((b, k), dtype=torch.float32, device=dev),
-                   ids=torch.empty((b, k), dtype=torch.int64, device=dev),
-                   count=torch.empty(b, dtype=torch.int32, device=dev),
-                   flags=torch.empty(b, dtype=torch.int32, device=dev))
+        out = TopK.empty(b, k, dev, rank=False)
         if b == 0:
             return out
-        need = self.workspace_bytes(b, k)
-        if workspace is None or workspace.numel() < need:
-            workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        workspace = _workspace(workspace, self.workspace_bytes(b, k), dev)
         call("armi_sparse_topk", self._handle, ptr(q_indptr), ptr(q_indices), ptr(q_values), b, k,
              ptr(row_mask), ptr(out.scores), ptr(out.ids), ptr(out.count), ptr(out.flags),
              ptr(workspace), workspace.numel(), stream_handle())
@@ -396,26 +400,17 @@ class SparseIndex:
         """Sparse dot top-k of every query over the rows of its list, from this index's forward
         CSR (armi_sparse_rowlist_topk; the list arguments as DenseIndex.topk_rows): the same
         ranking and scores as topk(row_mask=...), flags ARMI_FLAG_ROWLIST."""
-        if not 1 <= k <= MAX_K:
-            raise ValueError(f"k must be in [1, {MAX_K}]")
-        for t, dt, name in ((q_indptr, torch.int32, "q_indptr"), (q_indices, torch.int32, "q_indices"),
-                            (q_values, torch.float32, "q_values")):
-            if t.dtype != dt or t.dim() != 1 or not t.is_cuda or not t.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous 1-D {dt} device tensor")
+        _check_k(k)
+        _check_query_csr(q_indptr, q_indices, q_values)
         b = int(q_indptr.numel()) - 1
         dev = self.device
         n_lists = _check_row_lists(list_ptr, list_rows, q_list, max(b, 0), int(max_list_rows),
                                    self.n_rows, dev)
         list_ptr, list_rows, q_list = (_on_device(t, dev) for t in (list_ptr, list_rows, q_list))
-        out = TopK(scores=torch.empty((max(b, 0), k), dtype=torch.float32, device=dev),
-                   ids=torch.empty((max(b, 0), k), dtype=torch.int64, device=dev),
-                   count=torch.empty(max(b, 0), dtype=torch.int32, device=dev),
-                   flags=torch.empty(max(b, 0), dtype=torch.int32, device=dev))
+        out = TopK.empty(max(b, 0), k, dev, rank=False)
         if b <= 0:
             return out
-        need = self.rowlist_workspace_bytes(b, k, max_list_rows)
-        if workspace is None or workspace.numel() < need:
-            workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        workspace = _workspace(workspace, self.rowlist_workspace_bytes(b, k, max_list_rows), dev)
         with torch.cuda.device(dev):
             call("armi_sparse_rowlist_topk", ptr(self.indptr), ptr(self.indices), ptr(self.values),
                  self.n_rows, self.ordinal_base, ptr(q_indptr), ptr(q_indices), ptr(q_values), b, k,
@@ -530,12 +525,8 @@ class TailSparseIndex:
         topk of the same queries and k (armi_sparse_tail_topk). row_mask: bit r = row r of this
         segment. ARMI_TAIL_PASS=general (read per call) computes the same answer by topk() over
         the tail and a merge of the two lists."""
-        if not 1 <= k <= MAX_K:
-            raise ValueError(f"k must be in [1, {MAX_K}]")
-        for t, dt, name in ((q_indptr, torch.int32, "q_indptr"), (q_indices, torch.int32, "q_indices"),
-                            (q_values, torch.float32, "q_values")):
-            if t.dtype != dt or t.dim() != 1 or not t.is_cuda or not t.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous 1-D {dt} device tensor")
+        _check_k(k)
+        _check_query_csr(q_indptr, q_indices, q_values)
         b = int(q_indptr.numel()) - 1
         indptr, indices, values, n_rows = self._csr
         dev = indptr.device
@@ -564,15 +555,11 @@ class TailSparseIndex:
                              torch.stack([main.count, t.count]), k)
             m.flags = main.flags
             return m
-        out = TopK(scores=torch.empty((b, k), dtype=torch.float32, device=dev),
-                   ids=torch.empty((b, k), dtype=torch.int64, device=dev),
-                   count=torch.empty(b, dtype=torch.int32, device=dev),
-                   flags=torch.empty(b, dtype=torch.int32, device=dev))
+        out = TopK.empty(b, k, dev, rank=False)
         if b == 0:
             return out
         need = int(query("armi_sparse_tail_workspace_bytes", n_rows, b, k))
-        if workspace is None or workspace.numel() < need:
-            workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        workspace = _workspace(workspace, need, dev)
         m_scores, m_ids, m_count = (t.contiguous() for t in (main.scores, main.ids, main.count))
         m_flags = None if main.flags is None else main.flags.contiguous()
         with torch.cuda.device(dev):
@@ -592,10 +579,7 @@ def merge_shards(rank: torch.Tensor, scores: torch.Tensor, ids: torch.Tensor, co
     """Global top-k from per-shard lists [S, B, k_in] (+ count [S, B]) gathered from all ranks."""
     s, b, k_in = ids.shape
     dev = ids.device
-    out = TopK(scores=torch.empty((b, k_out), dtype=torch.float32, device=dev),
-               ids=torch.empty((b, k_out), dtype=torch.int64, device=dev),
-               rank=torch.empty((b, k_out), dtype=torch.float64, device=dev),
-               count=torch.empty(b, dtype=torch.int32, device=dev))
+    out = TopK.empty(b, k_out, dev, rank=True, flags=False)
     # hold the contiguous copies until the launch is enqueued (a freed temporary's block can be
     # handed to the next allocation before the kernel reads it)
     rank, scores, ids, count = (t.contiguous() for t in (rank, scores, ids, count))
@@ -614,10 +598,7 @@ def merge_shards_packed(buf: torch.Tensor, row0: int, n_queries: int, offsets: t
     if not buf.is_contiguous():
         raise ValueError("merge_shards_packed: the exchange buffer must be contiguous")
     dev = buf.device
-    out = TopK(scores=torch.empty((n_queries, k_out), dtype=torch.float32, device=dev),
-               ids=torch.empty((n_queries, k_out), dtype=torch.int64, device=dev),
-               rank=torch.empty((n_queries, k_out), dtype=torch.float64, device=dev),
-               count=torch.empty(n_queries, dtype=torch.int32, device=dev))
+    out = TopK.empty(n_queries, k_out, dev, rank=True, flags=False)
     off_rank, off_scores, off_ids, off_count = offsets
     call("armi_topk_merge_shards_packed", buf.data_ptr() + row0 * w, rows * w, w, off_rank,
          off_scores, off_ids, off_count, s, n_queries, k_in, k_out, ptr(out.rank),
