@@ -95,11 +95,18 @@ __device__ __forceinline__ f32x16 mfma16(u32x4 a, u32x4 b, f32x16 c) {
 // this access shape ran the scan at 3.3 TB/s instead of 5.4 TB/s.
 __device__ __forceinline__ u32x4 stream_load(const u32x4* p) { return *p; }
 
-// LDS bytes of the scans' workgroup merge scratch: lkey / lrow [kQB][65] (rows padded to 65 dwords)
-// and ldisc [kQB][17]. At dim 256 it is larger than the query image; sized without the padding it
-// left the discard bounds of the block's last queries past the allocation (reads of 0: a bound
-// that certified wrong lists).
-constexpr int kScanMergeScratch = kQB * 65 * 4 * 2 + kQB * 17 * 4;
+// Layout of the scans' workgroup merge scratch (scan_wg_merge): lkey / lrow [kQB][kListStride]
+// and ldisc [kQB][kDiscStride]. A query's row holds the kLaneList entries of its 2 * kWaves lane
+// lists (one wave's worth) plus one pad dword: lanes r = 0..31 write query r's row at the same
+// column, so an unpadded 64-dword stride put all 32 stores of an instruction in one bank. At dim
+// 256 the scratch is larger than the query image; sized without the padding it left the discard
+// bounds of the block's last queries past the allocation (reads of 0: a bound that certified
+// wrong lists), so the size and the pointers come from the same two strides.
+constexpr int kListSlots = 2 * kWaves;                        // lane lists per query (wave, half)
+constexpr int kListStride = kListSlots * kLaneList + 1;       // 65 dwords
+constexpr int kDiscStride = kListSlots + 1;                   // 17 dwords
+constexpr int kScanMergeScratch = kQB * kListStride * 4 * 2 + kQB * kDiscStride * 4;
+static_assert(kListSlots * kLaneList == 64, "a wave sorts one query's lane-list entries");
 
 // LDS bytes of the scan kernel: the query fragment image, later overlaid by the merge scratch.
 template <int DIM>
@@ -119,6 +126,201 @@ constexpr int i8_img_bytes() {
   constexpr int img = kQB * i8_qstride<DIM>();
   return img > kScanMergeScratch ? img : kScanMergeScratch;
 }
+// LDS bytes of dense_scan_i8_kernel: the image, then qnorm [kQB], qsel / qthr [kQB] each (collect
+// pass) and wcnt [kWaves].
+template <int DIM>
+constexpr int scan_i8_lds_bytes() {
+  return i8_img_bytes<DIM>() + kQB * 4 + kQB * 8 + kWaves * 4;
+}
+
+// ------------------------------------------------------------- pieces shared by the dense scans
+// dense_scan_kernel, scan_i8_body and dense_tail_scan_kernel are built from the helpers below; the
+// tail pass relies on the scan's certificate |approx - exact| <= delta for its approximate keys,
+// which holds because both run fp16_tile_mma and row_scales.
+
+// workgroup -> (64-query block qb, tile range rp). With several blocks, the blocks of one range
+// get workgroup ids congruent mod 8, i.e. the same XCD: they stream the same rows at about the
+// same time, so one block's HBM read is the others' L2 hit. (Host side: scan_grid.)
+__device__ __forceinline__ void scan_block(int bid, int n_qb, int& qb, int& rp) {
+  qb = 0;
+  rp = bid;
+  if (n_qb > 1) {
+    const int xcd = bid & 7, j = bid >> 3;
+    qb = j % n_qb;
+    rp = (j / n_qb) * 8 + xcd;
+  }
+}
+
+// The fp16 query fragment image [DIM / 16][2][kQB] of 16-byte fragments. K-step s, lane half h
+// takes the 8 elements of chunk c = 8*(s/4) + 4*h + s%4, matching the corpus chunk that lane half
+// loads (any k order is valid for a dot product as long as A and B agree). Queries past nq are
+// zero. A thread stages chunks of one query (kThreads is a multiple of kQB: q = lane);
+// on_chunk(v) sees each chunk it stored.
+template <int DIM, class F>
+__device__ __forceinline__ void stage_query_frags(u32x4* qimg, const uint16_t* __restrict__ queries,
+                                                  int nq, F on_chunk) {
+  static_assert(kThreads % kQB == 0 && kQB == 64, "one query per staging thread");
+  for (int e = threadIdx.x; e < (DIM / 16) * 2 * kQB; e += kThreads) {
+    const int q = e & (kQB - 1);
+    const int sh = e >> 6;
+    const int h = sh & 1;
+    const int s = sh >> 1;
+    const int c = 8 * (s >> 2) + 4 * h + (s & 3);
+    u32x4 v = {0u, 0u, 0u, 0u};
+    if (q < nq) v = *reinterpret_cast<const u32x4*>(queries + (size_t)q * DIM + 8 * c);
+    qimg[e] = v;
+    on_chunk(v);
+  }
+}
+
+// One 32-row tile against the 64 queries of the fragment image: acc0 / acc1 = the lane's 16 rows
+// x queries r / 32 + r. buf holds the tile's first kDepth 64-byte groups on entry (of the lane's
+// row at cur) and those of the row at nxt on exit; a caller without a next tile passes any valid
+// row, so every path issues the same loads. iv4 = inv_tile[8 q + 4 h ..], the inverse norms of
+// the lane's 16 rows.
+template <int DIM>
+__device__ __forceinline__ void fp16_tile_mma(u32x4 (&buf)[kDepth][4], const u32x4* cur,
+                                              const u32x4* nxt, const u32x4* qimg, int h, int r,
+                                              const float* __restrict__ inv_tile,
+                                              float4 (&iv4)[4], f32x16& acc0, f32x16& acc1) {
+  constexpr int GROUPS = DIM / 64;
+  static_assert(GROUPS % kDepth == 0, "prefetch ring must divide the tile");
+  // The fragment image is loop-invariant; an opaque per-tile offset keeps the compiler from
+  // hoisting all 2*KSTEPS fragment reads out of the tile loop (512 VGPRs -> scratch).
+  int qoff = h * kQB + r;
+  asm volatile("" : "+v"(qoff));
+  const u32x4* qv = qimg + qoff;
+  acc0 = {};
+  acc1 = {};
+#pragma unroll
+  for (int g = 0; g < GROUPS; ++g) {
+    u32x4 a[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) a[i] = buf[g % kDepth][i];
+    if (g == GROUPS - kDepth) {
+      // the inverse norms go out before the next tile's loads (an epilogue load issued after the
+      // prefetch would be waited for with a vmcnt(0) that drains the prefetch at every tile)
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        iv4[q] = *reinterpret_cast<const float4*>(inv_tile + 8 * q + 4 * h);
+    }
+    if (g + kDepth < GROUPS) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) buf[g % kDepth][i] = stream_load(cur + 8 * (g + kDepth) + i);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        buf[g % kDepth][i] = stream_load(nxt + 8 * (g + kDepth - GROUPS) + i);
+    }
+    // Pin the refill here: without it the scheduler sinks each load next to its first use
+    // (kDepth groups later) and every group waits a full HBM round trip.
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int s = 4 * g + i;
+      const u32x4 b0 = qv[s * 2 * kQB];
+      const u32x4 b1 = qv[s * 2 * kQB + 32];
+      acc0 = mfma16(a[i], b0, acc0);
+      acc1 = mfma16(a[i], b1, acc1);
+    }
+  }
+}
+
+// The scales of the lane's 16 rows (j: row (j&3) + 8*(j>>2) + 4*h of the tile at row0) from their
+// four loaded float4. Invalid rows carry a NaN scale, filtered rows get one here: a NaN score
+// never enters a lane list or reaches a threshold (x > s and x >= thr are false) and fmaxf ignores
+// it in the maxima and the bound, i.e. the lists and bounds of a -inf score without per-score
+// tests.
+__device__ __forceinline__ void row_scales(const float4 (&iv4)[4],
+                                           const uint64_t* __restrict__ row_mask, int64_t row0,
+                                           int h, float (&out)[16]) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const float4 v = iv4[q];
+    out[4 * q + 0] = v.x; out[4 * q + 1] = v.y; out[4 * q + 2] = v.z; out[4 * q + 3] = v.w;
+  }
+  if (row_mask) {
+    const uint32_t mbits = (uint32_t)(row_mask[row0 >> 6] >> (row0 & 63));
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+      if (!((mbits >> ((j & 3) + 8 * (j >> 2) + 4 * h)) & 1u)) out[j] = __builtin_nanf("");
+  }
+}
+
+// Offers a tile's 16 scores of one query (mx: their maximum) to the lane's list; score j belongs
+// to row id row_base + p * row_stride, p = (j&3) + 8*(j>>2). The wave skips the tile, or a row,
+// that no lane's list takes: its scores only raise the discard bound d.
+__device__ __forceinline__ void lane_lists_take(const float (&x)[16], float mx, int32_t row_base,
+                                                int32_t row_stride, float (&s)[kLaneList],
+                                                int32_t (&ix)[kLaneList], float& d) {
+  if (__any(mx > s[kLaneList - 1])) {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      if (!__any(x[j] > s[kLaneList - 1])) {
+        d = fmaxf(d, x[j]);  // = topm_insert of a value no lane list takes
+        continue;
+      }
+      topm_insert<kLaneList>(x[j], row_base + ((j & 3) + 8 * (j >> 2)) * row_stride, s, ix, d);
+    }
+  } else {
+    d = fmaxf(d, mx);
+  }
+}
+
+// Workgroup merge of a first pass: the kListSlots lane lists of each query (lane: queries r and
+// 32 + r, lists s0 / s1, discards d0 / d1) become its kKW best candidates and the bound, the
+// largest score any list discarded, at cand_*[out_base + q]. smem: kScanMergeScratch bytes that
+// overlay the (dead) query image.
+__device__ __forceinline__ void scan_wg_merge(
+    unsigned char* smem, int wave, int lane, const float (&s0)[kLaneList],
+    const int32_t (&i0)[kLaneList], float d0, const float (&s1)[kLaneList],
+    const int32_t (&i1)[kLaneList], float d1, int nq, size_t out_base,
+    float* __restrict__ cand_key, int32_t* __restrict__ cand_row, float* __restrict__ cand_bound) {
+  const int r = lane & 31;
+  const int h = lane >> 5;
+  __syncthreads();
+  float* lkey = reinterpret_cast<float*>(smem);                                // [kQB][kListStride]
+  int32_t* lrow = reinterpret_cast<int32_t*>(smem + kQB * kListStride * 4);    // [kQB][kListStride]
+  float* ldisc = reinterpret_cast<float*>(smem + kQB * kListStride * 8);       // [kQB][kDiscStride]
+  const int slot = wave * 2 + h;
+#pragma unroll
+  for (int j = 0; j < kLaneList; ++j) {
+    lkey[r * kListStride + slot * kLaneList + j] = s0[j];
+    lrow[r * kListStride + slot * kLaneList + j] = i0[j];
+    lkey[(32 + r) * kListStride + slot * kLaneList + j] = s1[j];
+    lrow[(32 + r) * kListStride + slot * kLaneList + j] = i1[j];
+  }
+  ldisc[r * kDiscStride + slot] = d0;
+  ldisc[(32 + r) * kDiscStride + slot] = d1;
+  __syncthreads();
+  // each wave merges its kQB / kWaves queries together (interleaved shuffle chains)
+  constexpr int QW = kQB / kWaves;
+  float key[QW], b[QW];
+  int32_t row[QW];
+#pragma unroll
+  for (int qq = 0; qq < QW; ++qq) {
+    const int q = wave * QW + qq;
+    key[qq] = lkey[q * kListStride + lane];
+    row[qq] = lrow[q * kListStride + lane];
+    b[qq] = (lane < kListSlots) ? ldisc[q * kDiscStride + lane] : kNegInf;
+  }
+  armi::wave_sort_approx_desc_n<QW>(key, row);
+#pragma unroll
+  for (int qq = 0; qq < QW; ++qq)
+    if (lane == kKW) b[qq] = fmaxf(b[qq], key[qq]);
+  armi::wave_max_all_n<QW>(b);
+#pragma unroll
+  for (int qq = 0; qq < QW; ++qq) {
+    const int q = wave * QW + qq;
+    if (q >= nq) break;
+    const size_t base = out_base + q;
+    if (lane < kKW) {
+      cand_key[base * kKW + lane] = key[qq];
+      cand_row[base * kKW + lane] = row[qq];
+    }
+    if (lane == 0) cand_bound[base] = b[qq];
+  }
+}
 
 template <int DIM>
 __global__ __launch_bounds__(kThreads) void dense_scan_kernel(
@@ -126,24 +328,15 @@ __global__ __launch_bounds__(kThreads) void dense_scan_kernel(
     const uint64_t* __restrict__ row_mask, int64_t n_rows, int64_t n_tiles, int tiles_per_wg,
     int n_ranges, int n_qb, const uint16_t* __restrict__ queries_all, int q_stride,
     float* __restrict__ cand_key, int32_t* __restrict__ cand_row, float* __restrict__ cand_bound) {
-  constexpr int KSTEPS = DIM / 16;
-  // workgroup -> (64-query block qb, tile range rp). With several blocks, the blocks of one range
-  // get workgroup ids congruent mod 8, i.e. the same XCD: they stream the same rows at about the
-  // same time, so one block's HBM read is the others' L2 hit.
-  int qb = 0, rp = blockIdx.x;
-  if (n_qb > 1) {
-    const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-    qb = j % n_qb;
-    rp = (j / n_qb) * 8 + xcd;
-  }
+  static_assert(scan_lds_bytes<DIM>() >= kScanMergeScratch, "the merge overlays the query image");
+  int qb, rp;
+  scan_block(blockIdx.x, n_qb, qb, rp);
   if (rp >= n_ranges) return;  // workgroup-uniform, before any barrier
   const int q0 = qb * kQB;
   const int nq = min(kQB, q_stride - q0);
   const uint16_t* __restrict__ queries = queries_all + (size_t)q0 * DIM;
-  constexpr int GROUPS = DIM / 64;
-  static_assert(GROUPS % kDepth == 0, "prefetch ring must divide the tile");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  u32x4* qimg = reinterpret_cast<u32x4*>(smem);  // [KSTEPS][2][kQB] 16-byte fragments
+  u32x4* qimg = reinterpret_cast<u32x4*>(smem);  // stage_query_frags' image
 
   const int wave = armi::wave_id();
   const int lane = threadIdx.x & 63;
@@ -168,19 +361,8 @@ __global__ __launch_bounds__(kThreads) void dense_scan_kernel(
       for (int i = 0; i < 4; ++i) buf[g][i] = stream_load(cur + 8 * g + i);
   }
 
-  // 1. Query fragment image. K-step s, lane half h takes the 8 elements of chunk
-  //    c = 8*(s/4) + 4*h + s%4, matching the corpus chunk that lane half loads (any k order
-  //    is valid for a dot product as long as A and B agree).
-  for (int e = threadIdx.x; e < KSTEPS * 2 * kQB; e += kThreads) {
-    const int q = e & (kQB - 1);
-    const int sh = e >> 6;
-    const int h = sh & 1;
-    const int s = sh >> 1;
-    const int c = 8 * (s >> 2) + 4 * h + (s & 3);
-    u32x4 v = {0u, 0u, 0u, 0u};
-    if (q < nq) v = *reinterpret_cast<const u32x4*>(queries + (size_t)q * DIM + 8 * c);
-    qimg[e] = v;
-  }
+  // 1. Query fragment image.
+  stage_query_frags<DIM>(qimg, queries, nq, [](u32x4) {});
   __syncthreads();
 
   float s0[kLaneList], s1[kLaneList];
@@ -195,64 +377,15 @@ __global__ __launch_bounds__(kThreads) void dense_scan_kernel(
     for (; t < t_end; t += kWaves) {
       const int64_t tn = (t + kWaves < t_end) ? t + kWaves : 0;  // (tile 0: shared, L2-hot)
       const u32x4* nxt = row_ptr(tn);
-      // The fragment image is loop-invariant; an opaque per-tile offset keeps the compiler from
-      // hoisting all 2*KSTEPS fragment reads out of the tile loop (512 VGPRs -> scratch).
-      int qoff = h * kQB + r;
-      asm volatile("" : "+v"(qoff));
-      const u32x4* qv = qimg + qoff;
-      f32x16 acc0 = {}, acc1 = {};
-      float4 iv4[4];  // inverse norms of the lane's 16 rows, loaded before the next tile's loads
-#pragma unroll
-      for (int g = 0; g < GROUPS; ++g) {
-        u32x4 a[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) a[i] = buf[g % kDepth][i];
-        if (g == GROUPS - kDepth) {
-          // (an epilogue load issued after the prefetch would be waited for with a vmcnt(0)
-          // that drains the prefetch at every tile)
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-            iv4[q] = *reinterpret_cast<const float4*>(inv_norm32 + t * TILE_ROWS + 8 * q + 4 * h);
-        }
-        if (g + kDepth < GROUPS) {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) buf[g % kDepth][i] = stream_load(cur + 8 * (g + kDepth) + i);
-        } else {
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-            buf[g % kDepth][i] = stream_load(nxt + 8 * (g + kDepth - GROUPS) + i);
-        }
-        // Pin the refill here: without it the scheduler sinks each load next to its first use
-        // (kDepth groups later) and every group waits a full HBM round trip.
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int s = 4 * g + i;
-          const u32x4 b0 = qv[s * 2 * kQB];
-          const u32x4 b1 = qv[s * 2 * kQB + 32];
-          acc0 = mfma16(a[i], b0, acc0);
-          acc1 = mfma16(a[i], b1, acc1);
-        }
-      }
+      const int64_t row0 = t * TILE_ROWS;
+      f32x16 acc0, acc1;
+      float4 iv4[4];
+      fp16_tile_mma<DIM>(buf, cur, nxt, qimg, h, r, inv_norm32 + row0, iv4, acc0, acc1);
       cur = nxt;
 
       // Epilogue: lane holds rows (j&3) + 8*(j>>2) + 4*h of the tile, queries r and 32 + r.
-      const int64_t row0 = t * TILE_ROWS;
       float inv[16];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float4 v = iv4[q];
-        inv[4 * q + 0] = v.x; inv[4 * q + 1] = v.y; inv[4 * q + 2] = v.z; inv[4 * q + 3] = v.w;
-      }
-      // Invalid rows carry a NaN inverse norm, filtered rows get one here: a NaN score never
-      // enters a lane list (x > s is false) and fmaxf ignores it in the maxima and the bound,
-      // i.e. the lists and bounds of a -inf score without per-score tests.
-      if (row_mask) {
-        const uint32_t mbits = (uint32_t)(row_mask[row0 >> 6] >> (row0 & 63));
-#pragma unroll
-        for (int j = 0; j < 16; ++j)
-          if (!((mbits >> ((j & 3) + 8 * (j >> 2) + 4 * h)) & 1u)) inv[j] = __builtin_nanf("");
-      }
+      row_scales(iv4, row_mask, row0, h, inv);
       float x0[16], x1[16];
       float mx0 = kNegInf, mx1 = kNegInf;
 #pragma unroll
@@ -263,76 +396,14 @@ __global__ __launch_bounds__(kThreads) void dense_scan_kernel(
         mx1 = fmaxf(mx1, x1[j]);
       }
       const int32_t rbase = (int32_t)row0 + 4 * h;
-      if (__any(mx0 > s0[kLaneList - 1])) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-          if (!__any(x0[j] > s0[kLaneList - 1])) {
-            d0 = fmaxf(d0, x0[j]);  // = topm_insert of a value no lane list takes
-            continue;
-          }
-          topm_insert<kLaneList>(x0[j], rbase + (j & 3) + 8 * (j >> 2), s0, i0, d0);
-        }
-      } else {
-        d0 = fmaxf(d0, mx0);
-      }
-      if (__any(mx1 > s1[kLaneList - 1])) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-          if (!__any(x1[j] > s1[kLaneList - 1])) {
-            d1 = fmaxf(d1, x1[j]);  // = topm_insert of a value no lane list takes
-            continue;
-          }
-          topm_insert<kLaneList>(x1[j], rbase + (j & 3) + 8 * (j >> 2), s1, i1, d1);
-        }
-      } else {
-        d1 = fmaxf(d1, mx1);
-      }
+      lane_lists_take(x0, mx0, rbase, 1, s0, i0, d0);
+      lane_lists_take(x1, mx1, rbase, 1, s1, i1, d1);
     }
   }
 
   // 2. Workgroup merge (the query image is dead: overlay it).
-  __syncthreads();
-  float* lkey = reinterpret_cast<float*>(smem);                           // [kQB][65]
-  int32_t* lrow = reinterpret_cast<int32_t*>(smem + kQB * 65 * 4);        // [kQB][65]
-  float* ldisc = reinterpret_cast<float*>(smem + kQB * 65 * 8);           // [kQB][17]
-  const int slot = wave * 2 + h;
-#pragma unroll
-  for (int j = 0; j < kLaneList; ++j) {
-    lkey[r * 65 + slot * kLaneList + j] = s0[j];
-    lrow[r * 65 + slot * kLaneList + j] = i0[j];
-    lkey[(32 + r) * 65 + slot * kLaneList + j] = s1[j];
-    lrow[(32 + r) * 65 + slot * kLaneList + j] = i1[j];
-  }
-  ldisc[r * 17 + slot] = d0;
-  ldisc[(32 + r) * 17 + slot] = d1;
-  __syncthreads();
-  // each wave merges its kQB / kWaves queries together (interleaved shuffle chains)
-  constexpr int QW = kQB / kWaves;
-  float key[QW], b[QW];
-  int32_t row[QW];
-#pragma unroll
-  for (int qq = 0; qq < QW; ++qq) {
-    const int q = wave * QW + qq;
-    key[qq] = lkey[q * 65 + lane];
-    row[qq] = lrow[q * 65 + lane];
-    b[qq] = (lane < 16) ? ldisc[q * 17 + lane] : kNegInf;
-  }
-  armi::wave_sort_approx_desc_n<QW>(key, row);
-#pragma unroll
-  for (int qq = 0; qq < QW; ++qq)
-    if (lane == kKW) b[qq] = fmaxf(b[qq], key[qq]);
-  armi::wave_max_all_n<QW>(b);
-#pragma unroll
-  for (int qq = 0; qq < QW; ++qq) {
-    const int q = wave * QW + qq;
-    if (q >= nq) break;
-    const size_t base = (size_t)rp * q_stride + q0 + q;
-    if (lane < kKW) {
-      cand_key[base * kKW + lane] = key[qq];
-      cand_row[base * kKW + lane] = row[qq];
-    }
-    if (lane == 0) cand_bound[base] = b[qq];
-  }
+  scan_wg_merge(smem, wave, lane, s0, i0, d0, s1, i1, d1, nq, (size_t)rp * q_stride + q0,
+                cand_key, cand_row, cand_bound);
 }
 
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
@@ -399,25 +470,22 @@ __device__ __forceinline__ void scan_i8_body(
     const int32_t* __restrict__ tile_ord, const uint32_t* __restrict__ flags,
     const float* __restrict__ thr, int32_t* __restrict__ col_cnt, int32_t* __restrict__ col_list,
     int col_cap){
-  constexpr int KSTEPS = DIM / 16;  // MFMA k-steps
   constexpr int GROUPS = DIM / 128;  // 128-B groups of a row: 4 chunks per lane half
   constexpr int DEPTH = GROUPS % 4 == 0 ? 4 : 2;  // groups in flight per lane
-  int qb = 0, rp = bid;
-  if (n_qb > 1) {
-    const int xcd = bid & 7, j = bid >> 3;
-    qb = j % n_qb;
-    rp = (j / n_qb) * 8 + xcd;
-  }
+  static_assert(i8_img_bytes<DIM>() >= kScanMergeScratch &&
+                    scan_i8_lds_bytes<DIM>() >= i8_img_bytes<DIM>(),
+                "the merge overlays the query image");
+  int qb, rp;
+  scan_block(bid, n_qb, qb, rp);
   if (rp >= n_ranges) return;  // workgroup-uniform, before any barrier
   const int q0 = qb * kQB;
   int nq = min(kQB, q_stride - q0);
   const uint16_t* __restrict__ queries = queries_all + (size_t)q0 * DIM;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int QS = i8_qstride<DIM>();  // query row stride of the image (B)
+  // behind the image (scan_i8_lds_bytes):
   float* qnorm = reinterpret_cast<float*>(smem + (size_t)i8_img_bytes<DIM>());  // [kQB] |q| up
-  float* qscale = qnorm + kQB;  // (unused slot, keeps the layout of scan_i8_lds_bytes)
-  // (qscale + kQB: [8][kQB] unused slots, keep the layout of scan_i8_lds_bytes)
-  int32_t* qsel = reinterpret_cast<int32_t*>(qscale + kQB + kQB * (kThreads / kQB));  // [kQB] COLLECT
+  int32_t* qsel = reinterpret_cast<int32_t*>(qnorm + kQB);                   // [kQB] COLLECT
   float* qthr = reinterpret_cast<float*>(qsel + kQB);                        // [kQB] COLLECT
   int32_t* wcnt = reinterpret_cast<int32_t*>(qthr + kQB);                    // [kWaves]
 
@@ -665,18 +733,11 @@ __device__ __forceinline__ void scan_i8_body(
       // Epilogue: lane holds rows (j&3) + 8*(j>>2) + 4*h of the tile, queries r and 32 + r.
       const int64_t row0 = t * TILE_ROWS;
       float sc[16], ec[16];
+      row_scales(sv, row_mask, row0, h, sc);  // (NaN for invalid and filtered rows)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const float4 v = sv[q], w = ev[q];
-        sc[4 * q + 0] = v.x; sc[4 * q + 1] = v.y; sc[4 * q + 2] = v.z; sc[4 * q + 3] = v.w;
+        const float4 w = ev[q];
         ec[4 * q + 0] = w.x; ec[4 * q + 1] = w.y; ec[4 * q + 2] = w.z; ec[4 * q + 3] = w.w;
-      }
-      // invalid and filtered rows: NaN scale (never a lane-list entry, ignored by the bound)
-      if (row_mask) {
-        const uint32_t mbits = (uint32_t)(row_mask[row0 >> 6] >> (row0 & 63));
-#pragma unroll
-        for (int j = 0; j < 16; ++j)
-          if (!((mbits >> ((j & 3) + 8 * (j >> 2) + 4 * h)) & 1u)) sc[j] = __builtin_nanf("");
       }
       float x0[16], x1[16];
       float mx0 = kNegInf, mx1 = kNegInf;
@@ -710,80 +771,16 @@ __device__ __forceinline__ void scan_i8_body(
         }
         continue;
       }
-      if (__any(mx0 > s0[kLaneList - 1])) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-          if (!__any(x0[j] > s0[kLaneList - 1])) {
-            d0 = fmaxf(d0, x0[j]);
-            continue;
-          }
-          topm_insert<kLaneList>(x0[j], obase + ((j & 3) + 8 * (j >> 2)) * T32, s0, i0, d0);
-        }
-      } else {
-        d0 = fmaxf(d0, mx0);
-      }
-      if (__any(mx1 > s1[kLaneList - 1])) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-          if (!__any(x1[j] > s1[kLaneList - 1])) {
-            d1 = fmaxf(d1, x1[j]);
-            continue;
-          }
-          topm_insert<kLaneList>(x1[j], obase + ((j & 3) + 8 * (j >> 2)) * T32, s1, i1, d1);
-        }
-      } else {
-        d1 = fmaxf(d1, mx1);
-      }
+      lane_lists_take(x0, mx0, obase, T32, s0, i0, d0);
+      lane_lists_take(x1, mx1, obase, T32, s1, i1, d1);
     }
   }
 
   I8_STAMP(2);
   if constexpr (COLLECT) return;
-  // 2. Workgroup merge (as dense_scan_kernel; the query image is dead: overlay it). Rows of 65
-  // dwords: lanes r = 0..31 write query r's row at the same column, so a 64-dword stride put all
-  // 32 stores of an instruction in one bank
-  constexpr int kLS = 65;
-  __syncthreads();
-  float* lkey = reinterpret_cast<float*>(smem);                           // [kQB][kLS]
-  int32_t* lrow = reinterpret_cast<int32_t*>(smem + kQB * kLS * 4);       // [kQB][kLS]
-  float* ldisc = reinterpret_cast<float*>(smem + kQB * kLS * 8);          // [kQB][17]
-  const int slot = wave * 2 + h;
-#pragma unroll
-  for (int j = 0; j < kLaneList; ++j) {
-    lkey[r * kLS + slot * kLaneList + j] = s0[j];
-    lrow[r * kLS + slot * kLaneList + j] = i0[j];
-    lkey[(32 + r) * kLS + slot * kLaneList + j] = s1[j];
-    lrow[(32 + r) * kLS + slot * kLaneList + j] = i1[j];
-  }
-  ldisc[r * 17 + slot] = d0;
-  ldisc[(32 + r) * 17 + slot] = d1;
-  __syncthreads();
-  constexpr int QW = kQB / kWaves;
-  float key[QW], b[QW];
-  int32_t row[QW];
-#pragma unroll
-  for (int qq = 0; qq < QW; ++qq) {
-    const int q = wave * QW + qq;
-    key[qq] = lkey[q * kLS + lane];
-    row[qq] = lrow[q * kLS + lane];
-    b[qq] = (lane < 16) ? ldisc[q * 17 + lane] : kNegInf;
-  }
-  armi::wave_sort_approx_desc_n<QW>(key, row);
-#pragma unroll
-  for (int qq = 0; qq < QW; ++qq)
-    if (lane == kKW) b[qq] = fmaxf(b[qq], key[qq]);
-  armi::wave_max_all_n<QW>(b);
-#pragma unroll
-  for (int qq = 0; qq < QW; ++qq) {
-    const int q = wave * QW + qq;
-    if (q >= nq) break;
-    const size_t base = (size_t)rp * q_stride + q0 + q;
-    if (lane < kKW) {
-      cand_key[base * kKW + lane] = key[qq];
-      cand_row[base * kKW + lane] = row[qq];
-    }
-    if (lane == 0) cand_bound[base] = b[qq];
-  }
+  // 2. Workgroup merge (as dense_scan_kernel; the query image is dead: overlay it).
+  scan_wg_merge(smem, wave, lane, s0, i0, d0, s1, i1, d1, nq, (size_t)rp * q_stride + q0,
+                cand_key, cand_row, cand_bound);
   I8_STAMP(3);
 }
 
@@ -802,12 +799,6 @@ __global__ __launch_bounds__(kThreads) void dense_scan_i8_kernel(
   scan_i8_body<DIM, COLLECT, NT>(blockIdx.x / xcd_step, rows8, a32, e32, row_mask, n_rows, n_tiles, tiles_per_wg, n_ranges, n_qb,
       queries_all, q_stride, cand_key, cand_row, cand_bound, tile_ord, flags, thr, col_cnt,
       col_list, col_cap);
-}
-
-
-template <int DIM>
-constexpr int scan_i8_lds_bytes() {
-  return i8_img_bytes<DIM>() + kQB * 8 + kQB * 4 * (kThreads / kQB) + kQB * 8 + kWaves * 4;
 }
 
 // Multi-block scan for calls with more than 2 * kQB queries (the all-gathered batch of a sharded
@@ -2373,6 +2364,10 @@ struct ScanPlan {
   int kc = 0;
 };
 
+// Workgroups of a scan over n_wg tile ranges and n_qb query blocks: scan_block's mapping keeps the
+// blocks of a range on one XCD, so with several blocks the ranges are padded to a multiple of 8.
+int scan_grid(int n_qb, int n_wg) { return n_qb == 1 ? n_wg : n_qb * 8 * ((n_wg + 7) / 8); }
+
 ScanPlan plan_scan(const armi_index* idx, int k, int nq) {
   ScanPlan p;
   const int64_t tiles = std::max<int64_t>(idx->n_tiles, 1);
@@ -2387,7 +2382,7 @@ ScanPlan plan_scan(const armi_index* idx, int k, int nq) {
   const int64_t wgs = std::min<int64_t>(want, tiles);
   p.tiles_per_wg = (int)((tiles + wgs - 1) / wgs);
   p.n_wg = (int)((tiles + p.tiles_per_wg - 1) / p.tiles_per_wg);
-  p.grid = p.n_qb == 1 ? p.n_wg : p.n_qb * 8 * ((p.n_wg + 7) / 8);
+  p.grid = scan_grid(p.n_qb, p.n_wg);
   // Probe builds only (ARMI_BUILD_FLAGS=-DARMI_XCD_COMPACT): a single block of <= 64 workgroups
   // on two XCDs (workgroup i runs on XCD i mod 8; the others exit at once), so only two L2s fetch
   // the fp16 queries (128 KB each). At 10k rows that takes the scan's HBM traffic from 1.18 to
@@ -2703,7 +2698,7 @@ int dense_second_pass(const armi_index* idx, const uint16_t* queries, int nq, in
   {
     const ScanPlan cp = plan_scan(idx, k, 1);  // one block's ranges; blocks of one range share an XCD
     const int n_qb = (nq + kQB - 1) / kQB;
-    const int grid = n_qb == 1 ? cp.n_wg : n_qb * 8 * ((cp.n_wg + 7) / 8);
+    const int grid = scan_grid(n_qb, cp.n_wg);
     auto kern = use_nt_stream(idx) ? dense_scan_i8_kernel<DIM, true, true>
                                    : dense_scan_i8_kernel<DIM, true, false>;
     if (int rc = allow_lds(kern, scan_i8_lds_bytes<DIM>())) return rc;
@@ -2733,7 +2728,7 @@ int dense_second_pass(const armi_index* idx, const uint16_t* queries, int nq, in
 // its exact key reaches it, i.e. (|approx - exact| <= delta, the scan's certificate) when its
 // approximate key reaches thr = kth - delta rounded down (-inf when the main list holds fewer
 // than k). Two launches:
-//   dense_tail_scan    dense_scan_kernel's tile loop (same MFMA operands, same inv_norm32 scaling)
+//   dense_tail_scan    dense_scan_kernel's tile loop (fp16_tile_mma and row_scales themselves)
 //                      over 8 tiles per workgroup, with an epilogue that keeps no lane lists: a
 //                      (row, query) pair at or above the query's thr is appended to the
 //                      workgroup's own list of that query (256 slots = its rows: it cannot
@@ -2755,15 +2750,15 @@ __global__ __launch_bounds__(kThreads) void dense_tail_scan_kernel(
     const uint16_t* __restrict__ queries_all, int nq_all, int k,
     const double* __restrict__ main_rank, const int32_t* __restrict__ main_count,
     int32_t* __restrict__ wg_cnt, int32_t* __restrict__ wg_list) {
-  constexpr int KSTEPS = DIM / 16;
-  constexpr int GROUPS = DIM / 64;
-  static_assert(GROUPS % kDepth == 0, "prefetch ring must divide the tile");
+  static_assert(tail_scan_lds_bytes<DIM>() >= scan_lds_bytes<DIM>() &&
+                    scan_lds_bytes<DIM>() >= kScanMergeScratch,
+                "the fragment image (sized as the scan's, merge scratch included)");
   const int q0 = blockIdx.y * kQB;
   const int nq = min(kQB, nq_all - q0);
   const int n_wg = gridDim.x;
   const uint16_t* __restrict__ queries = queries_all + (size_t)q0 * DIM;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  u32x4* qimg = reinterpret_cast<u32x4*>(smem);  // [KSTEPS][2][kQB] 16-byte fragments
+  u32x4* qimg = reinterpret_cast<u32x4*>(smem);  // stage_query_frags' image
   float* s_thr = reinterpret_cast<float*>(smem + scan_lds_bytes<DIM>());       // [kQB]
   int* s_cnt = reinterpret_cast<int*>(smem + scan_lds_bytes<DIM>() + kQB * 4);  // [kQB]
   int64_t* s_n2 = reinterpret_cast<int64_t*>(smem + scan_lds_bytes<DIM>() + kQB * 8);  // [kWaves][kQB]
@@ -2788,27 +2783,17 @@ __global__ __launch_bounds__(kThreads) void dense_tail_scan_kernel(
 #pragma unroll
       for (int i = 0; i < 4; ++i) buf[g][i] = stream_load(cur + 8 * g + i);
   }
-  // the query fragment image of dense_scan_kernel (K-step s, lane half h: chunk 8*(s/4)+4*h+s%4).
-  // A thread stages chunks of one query (kThreads is a multiple of kQB: q = lane), so the exact
+  // the scan's query fragment image. A thread stages chunks of one query (q = lane), so the exact
   // query norms fall out of the same loads: the sum of squares of the thread's chunks, the eight
   // waves' partials of a query added through LDS (int64: any order gives the same bits).
-  static_assert(kThreads % kQB == 0 && kQB == 64, "one query per staging thread");
   int64_t n2 = 0;
-  for (int e = threadIdx.x; e < KSTEPS * 2 * kQB; e += kThreads) {
-    const int q = e & (kQB - 1);
-    const int sh = e >> 6;
-    const int hh = sh & 1;
-    const int s = sh >> 1;
-    const int c = 8 * (s >> 2) + 4 * hh + (s & 3);
-    u32x4 v = {0u, 0u, 0u, 0u};
-    if (q < nq) v = *reinterpret_cast<const u32x4*>(queries + (size_t)q * DIM + 8 * c);
-    qimg[e] = v;
+  stage_query_frags<DIM>(qimg, queries, nq, [&](u32x4 v) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int64_t lo = armi::fp16_to_fixed24(v[i] & 0xffffu), hi = armi::fp16_to_fixed24(v[i] >> 16);
       n2 += lo * lo + hi * hi;
     }
-  }
+  });
   s_n2[wave * kQB + lane] = n2;
   __syncthreads();
   // thresholds of the block's queries (+inf: no such query)
@@ -2837,57 +2822,17 @@ __global__ __launch_bounds__(kThreads) void dense_tail_scan_kernel(
   for (; t < t_end; t += kWaves) {
     const int64_t tn = (t + kWaves < t_end) ? t + kWaves : t_begin;
     const u32x4* nxt = row_ptr(tn);
-    int qoff = h * kQB + r;
-    asm volatile("" : "+v"(qoff));  // keeps the fragment reads inside the tile loop
-    const u32x4* qv = qimg + qoff;
-    f32x16 acc0 = {}, acc1 = {};
+    const int64_t row0 = t * TILE_ROWS;
+    f32x16 acc0, acc1;
     float4 iv4[4];
-#pragma unroll
-    for (int g = 0; g < GROUPS; ++g) {
-      u32x4 a[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) a[i] = buf[g % kDepth][i];
-      if (g == GROUPS - kDepth) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          iv4[q] = *reinterpret_cast<const float4*>(inv_norm32 + t * TILE_ROWS + 8 * q + 4 * h);
-      }
-      if (g + kDepth < GROUPS) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) buf[g % kDepth][i] = stream_load(cur + 8 * (g + kDepth) + i);
-      } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          buf[g % kDepth][i] = stream_load(nxt + 8 * (g + kDepth - GROUPS) + i);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int s = 4 * g + i;
-        const u32x4 b0 = qv[s * 2 * kQB];
-        const u32x4 b1 = qv[s * 2 * kQB + 32];
-        acc0 = mfma16(a[i], b0, acc0);
-        acc1 = mfma16(a[i], b1, acc1);
-      }
-    }
+    fp16_tile_mma<DIM>(buf, cur, nxt, qimg, h, r, inv_norm32 + row0, iv4, acc0, acc1);
     cur = nxt;
 
-    // Epilogue: lane holds rows (j&3) + 8*(j>>2) + 4*h of the tile, queries r and 32 + r. Padding
-    // and invalid rows carry a NaN inverse norm, filtered rows get one here: NaN >= thr is false.
+    // Epilogue: lane holds rows (j&3) + 8*(j>>2) + 4*h of the tile, queries r and 32 + r; padding,
+    // invalid and filtered rows have a NaN scale, and NaN >= thr is false.
     // (A (row, query) pair is seen once, so a workgroup's list takes at most its kTailWgRows rows.)
-    const int64_t row0 = t * TILE_ROWS;
     float inv[16];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float4 v = iv4[q];
-      inv[4 * q + 0] = v.x; inv[4 * q + 1] = v.y; inv[4 * q + 2] = v.z; inv[4 * q + 3] = v.w;
-    }
-    if (row_mask) {
-      const uint32_t mbits = (uint32_t)(row_mask[row0 >> 6] >> (row0 & 63));
-#pragma unroll
-      for (int j = 0; j < 16; ++j)
-        if (!((mbits >> ((j & 3) + 8 * (j >> 2) + 4 * h)) & 1u)) inv[j] = __builtin_nanf("");
-    }
+    row_scales(iv4, row_mask, row0, h, inv);
     const int32_t rbase = (int32_t)row0 + 4 * h;
 #pragma unroll
     for (int j = 0; j < 16; ++j) {

@@ -183,7 +183,9 @@ def test_exact_entry_point_matches_oracle(ctx, dim):
 
 
 MASKED = [("INT8_FILTER", 16, 5, False), ("FP16", 16, 65, False), ("TILED_FP16", 130, 5, False),
-          ("EXACT", 16, 5, True), ("EXACT", 130, 5, True)]
+          ("EXACT", 16, 5, True), ("EXACT", 130, 5, True),
+          # two 64-query blocks: the XCD-grouped workgroup mapping together with the row mask
+          ("INT8_FILTER", 100, 40, False), ("FP16", 70, 128, False)]
 
 
 @pytest.mark.parametrize("form,nq,k,exact", MASKED)
