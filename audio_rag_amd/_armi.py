@@ -23,9 +23,12 @@ ARMI_FLAG_CERTIFIED = 1
 ARMI_FLAG_FALLBACK = 2
 ARMI_FLAG_FILTERED = 4
 ARMI_FLAG_ROWLIST = 8
+ARMI_FLAG_QMASK = 16
+ARMI_ERR_INVALID, ARMI_ERR_HIP, ARMI_ERR_UNSUPPORTED = 1, 2, 3
 TIMING_DENSE_SCAN, TIMING_SPARSE_SCAN, TIMING_ENCODER_GEMM, TIMING_SPARSE_STAGE = 0, 1, 2, 3
+TIMING_QMASK_PREP = 4
 SCAN_FP16, SCAN_INT8_FILTER, SCAN_TILED_FP16, SCAN_TILED_INT8 = 0, 1, 2, 3  # armi_dense_scan_form
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 c_void_p = ctypes.c_void_p
 c_int = ctypes.c_int
@@ -73,6 +76,11 @@ SIGNATURES: dict[str, tuple] = {
     "armi_dense_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "armi_dense_topk": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "armi_dense_qmask_supported": (c_int, [c_void_p, c_int, c_int]),
+    "armi_dense_qmask_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
+    "armi_dense_topk_qmask": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p,
+                                      c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_size_t, c_void_p]),
     "armi_dense_exact_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "armi_dense_exact_topk": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

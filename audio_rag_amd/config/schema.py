@@ -74,6 +74,16 @@ class RetrievalConfig(BaseModel):
     # search is a masked scan, one per filter. Answers are the same either way. Ignored with
     # num_gpus > 1
     filter_list_rows: int = Field(default=0, ge=0)
+    # broad filters in one batch: True lets the queries of a search_batch call that carry
+    # different filters (or none) share one dense scan of the int8 image per 64 queries, each query
+    # under its own row mask (armi_dense_topk_qmask), instead of one masked search per filter.
+    # Applies to the groups filter_list_rows leaves to the masked scan when there are at least two
+    # of them, in dense and hybrid search (hybrid's sparse leg stays one search per filter), for a
+    # dense k <= 64 (hybrid: 2 * top_k), up to 128 queries per scan and a collection without tail
+    # rows; everything else (the sparse kernels, the fp16 scan of k > 64, the live tail pass, the
+    # native StreamServer) keeps one search per filter. False: as before. Answers are the same
+    # either way. Ignored with num_gpus > 1
+    filter_query_masks: bool = False
 
 
 class RerankingConfig(BaseModel):

@@ -461,7 +461,16 @@ __device__ uint64_t g_i8_stamps[256 * kWaves * 4];
 // reaches it is appended to the query's list: a row of the true top-k has exact >= k-th found,
 // hence key >= thr, so the list holds the whole top-k whatever the corpus looks like (runs of
 // near-duplicates, one-ulp neighbours, exact duplicates). dense_collect_merge_kernel rescores it.
-template <int DIM, bool COLLECT, bool NT>
+//
+// QMASK (armi_dense_topk_qmask): every query carries its own row filter. qmask_img is the call's
+// mask image [n_qb][n_tiles][kQB] of u32 (qmask_prep_kernel): word (qb, tau, c) holds at bit p the
+// filter bit of image row p of tile tau for query kQB * qb + c, so a tile's words for one query
+// block are one 256-B run. The lane's two words (its queries r and 32 + r; in the collect pass the
+// words of the uncertified queries dealt to those columns) go out with the tile's a32 / e32 loads
+// and a clear bit turns the SCORE into NaN before the tile maxima, the lane lists and the collect
+// threshold: the rule row_scales documents (a NaN enters no list, no bound and no >= thr), applied
+// per (row, query) instead of per row. row_mask is unused (null) in this form.
+template <int DIM, bool COLLECT, bool NT, bool QMASK = false>
 __device__ __forceinline__ void scan_i8_body(
     const int bid, const int8_t* __restrict__ rows8, const float* __restrict__ a32, const float* __restrict__ e32,
     const uint64_t* __restrict__ row_mask, int64_t n_rows, int64_t n_tiles, int tiles_per_wg,
@@ -469,7 +478,7 @@ __device__ __forceinline__ void scan_i8_body(
     float* __restrict__ cand_key, int32_t* __restrict__ cand_row, float* __restrict__ cand_bound,
     const int32_t* __restrict__ tile_ord, const uint32_t* __restrict__ flags,
     const float* __restrict__ thr, int32_t* __restrict__ col_cnt, int32_t* __restrict__ col_list,
-    int col_cap){
+    int col_cap, const uint32_t* __restrict__ qmask_img = nullptr){
   constexpr int GROUPS = DIM / 128;  // 128-B groups of a row: 4 chunks per lane half
   constexpr int DEPTH = GROUPS % 4 == 0 ? 4 : 2;  // groups in flight per lane
   static_assert(i8_img_bytes<DIM>() >= kScanMergeScratch &&
@@ -626,6 +635,18 @@ __device__ __forceinline__ void scan_i8_body(
     qi0 = qsel[r];
     qi1 = qsel[32 + r];
   }
+  // QMASK: the lane's two words of a tile's mask run, as offsets from the tile's (block 0) run
+  int64_t mo0 = 0, mo1 = 0;
+  if constexpr (QMASK) {
+    const int64_t blk = n_tiles * kQB;  // words of one query block's image
+    if constexpr (COLLECT) {
+      mo0 = (int64_t)(qi0 >> 6) * blk + (qi0 & (kQB - 1));
+      mo1 = (int64_t)(qi1 >> 6) * blk + (qi1 & (kQB - 1));
+    } else {
+      mo0 = (int64_t)qb * blk + r;
+      mo1 = mo0 + 32;
+    }
+  }
 
   float s0[kLaneList], s1[kLaneList];
   int32_t i0[kLaneList], i1[kLaneList];
@@ -655,6 +676,7 @@ __device__ __forceinline__ void scan_i8_body(
       const u32x4* nxt = cur;
       bool has_next = false;
       float4 sv[4], ev[4];  // a32 / e32 of the lane's 16 rows (loaded mid-tile)
+      uint32_t mk0 = 0, mk1 = 0;  // QMASK: the tile's mask words of the lane's two queries
       const int32_t tord = tile_ord[t];  // ordinal of the tile's image row 0 (wave-uniform)
       // the lane's two query rows in the image (queries r and 32 + r, chunk half h)
       int qoff = r * QS + h * 128;
@@ -689,6 +711,11 @@ __device__ __forceinline__ void scan_i8_body(
           for (int q = 0; q < 4; ++q) {
             sv[q] = *reinterpret_cast<const float4*>(a32 + r0s + 8 * q + 4 * h);
             ev[q] = *reinterpret_cast<const float4*>(e32 + r0s + 8 * q + 4 * h);
+          }
+          if constexpr (QMASK) {  // (with the scales: in flight across the rest of the k-loop)
+            const uint32_t* mrun = qmask_img + t * kQB;
+            mk0 = mrun[mo0];
+            mk1 = mrun[mo1];
           }
         }
         u32x4 a[4];
@@ -733,7 +760,7 @@ __device__ __forceinline__ void scan_i8_body(
       // Epilogue: lane holds rows (j&3) + 8*(j>>2) + 4*h of the tile, queries r and 32 + r.
       const int64_t row0 = t * TILE_ROWS;
       float sc[16], ec[16];
-      row_scales(sv, row_mask, row0, h, sc);  // (NaN for invalid and filtered rows)
+      row_scales(sv, QMASK ? nullptr : row_mask, row0, h, sc);  // (NaN: invalid, filtered rows)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const float4 w = ev[q];
@@ -745,6 +772,11 @@ __device__ __forceinline__ void scan_i8_body(
       for (int j = 0; j < 16; ++j) {
         x0[j] = __builtin_fmaf(acc0[j], sc[j], ec[j] * qn0);
         x1[j] = __builtin_fmaf(acc1[j], sc[j], ec[j] * qn1);
+        if constexpr (QMASK) {  // the lane's rows are bits (j&3) + 8*(j>>2) + 4*h of the words
+          const int p = (j & 3) + 8 * (j >> 2);
+          if (!(((mk0 >> (4 * h)) >> p) & 1u)) x0[j] = __builtin_nanf("");
+          if (!(((mk1 >> (4 * h)) >> p) & 1u)) x1[j] = __builtin_nanf("");
+        }
         mx0 = fmaxf(mx0, x0[j]);
         mx1 = fmaxf(mx1, x1[j]);
       }
@@ -799,6 +831,22 @@ __global__ __launch_bounds__(kThreads) void dense_scan_i8_kernel(
   scan_i8_body<DIM, COLLECT, NT>(blockIdx.x / xcd_step, rows8, a32, e32, row_mask, n_rows, n_tiles, tiles_per_wg, n_ranges, n_qb,
       queries_all, q_stride, cand_key, cand_row, cand_bound, tile_ord, flags, thr, col_cnt,
       col_list, col_cap);
+}
+
+// The per-query-mask form (scan_i8_body<QMASK>): the same kernel with the mask image in place of
+// the shared row mask. A kernel of its own, so the instances above keep their arguments and code.
+template <int DIM, bool COLLECT, bool NT>
+__global__ __launch_bounds__(kThreads) void dense_scan_i8_qmask_kernel(
+    const int8_t* __restrict__ rows8, const float* __restrict__ a32, const float* __restrict__ e32,
+    const uint32_t* __restrict__ qmask_img, int64_t n_rows, int64_t n_tiles, int tiles_per_wg,
+    int n_ranges, int n_qb, const uint16_t* __restrict__ queries_all, int q_stride,
+    float* __restrict__ cand_key, int32_t* __restrict__ cand_row, float* __restrict__ cand_bound,
+    const int32_t* __restrict__ tile_ord, const uint32_t* __restrict__ flags,
+    const float* __restrict__ thr, int32_t* __restrict__ col_cnt, int32_t* __restrict__ col_list,
+    int col_cap) {
+  scan_i8_body<DIM, COLLECT, NT, true>(blockIdx.x, rows8, a32, e32, nullptr, n_rows, n_tiles,
+      tiles_per_wg, n_ranges, n_qb, queries_all, q_stride, cand_key, cand_row, cand_bound, tile_ord,
+      flags, thr, col_cnt, col_list, col_cap, qmask_img);
 }
 
 // Multi-block scan for calls with more than 2 * kQB queries (the all-gathered batch of a sharded
@@ -2117,7 +2165,8 @@ __device__ __forceinline__ void collect_merge_body(
     const uint64_t* __restrict__ row_mask, int64_t n_rows, const uint16_t* __restrict__ queries,
     const double* __restrict__ inv_q, int k, int64_t ordinal_base, float* __restrict__ out_scores,
     int64_t* __restrict__ out_ids, double* __restrict__ out_rank, int32_t* __restrict__ out_count,
-    uint32_t* __restrict__ flags){
+    uint32_t* __restrict__ flags, const int32_t* __restrict__ q_mask = nullptr, int n_masks = 0,
+    int64_t mask_stride = 0, uint32_t flag_or = 0u){
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   double* key = reinterpret_cast<double*>(smem);                            // [2 * kColChunk]
   int64_t* ord = reinterpret_cast<int64_t*>(smem + 2 * kColChunk * 8);       // [2 * kColChunk]
@@ -2127,17 +2176,28 @@ __device__ __forceinline__ void collect_merge_body(
   auto write_out = [&](int qg) {
     armi::write_top_k(key, ord, qg, k, armi::ScoreTimes{inv_q[qg]}, out_scores, out_ids, out_rank,
                       out_count);
-    if (tid == 0) flags[qg] = ARMI_FLAG_FALLBACK;
+    if (tid == 0) flags[qg] = ARMI_FLAG_FALLBACK | flag_or;
+  };
+  // q_mask (armi_dense_topk_qmask): row_mask is the call's [n_masks][mask_stride] masks and the
+  // helpers filter by the query's own (none for -1 and for an entry outside [0, n_masks))
+  auto mask_of = [&](int qg) -> const uint64_t* {
+    if (!q_mask) return row_mask;
+    const int m = q_mask[qg];
+    return m >= 0 && m < n_masks ? row_mask + (int64_t)m * mask_stride : nullptr;
   };
   if (bid < nq) {  // the query's own workgroup
     const int qg = bid;
-    if (flags[qg] & ARMI_FLAG_CERTIFIED) return;  // workgroup-uniform
+    if (flags[qg] & ARMI_FLAG_CERTIFIED) {  // workgroup-uniform
+      // (the helpers test the CERTIFIED bit of this word only: it stays set)
+      if (flag_or && tid == 0) flags[qg] = ARMI_FLAG_CERTIFIED | flag_or;
+      return;
+    }
     const int cnt = col_cnt[qg];
     if (cnt > col_cap) return;  // overflowed: the helpers answer it
     int32_t qf[DIM / 64];
     load_fixed<DIM>(queries + (size_t)qg * DIM, lane, qf);
     collect_top_rows<DIM>(col_list + (size_t)qg * col_cap, 0, cnt, k, qf, rows, inv_norm, norm2,
-                          row_mask, ordinal_base, key, ord);
+                          row_mask, ordinal_base, key, ord);  // (a list: the mask is not read)
     write_out(qg);
     return;
   }
@@ -2155,7 +2215,7 @@ __device__ __forceinline__ void collect_merge_body(
     if ((flags[qg] & ARMI_FLAG_CERTIFIED) || col_cnt[qg] <= col_cap) continue;  // uniform
     int32_t qf[DIM / 64];
     load_fixed<DIM>(queries + (size_t)qg * DIM, lane, qf);
-    collect_top_rows<DIM>(nullptr, lo, hi - lo, k, qf, rows, inv_norm, norm2, row_mask,
+    collect_top_rows<DIM>(nullptr, lo, hi - lo, k, qf, rows, inv_norm, norm2, mask_of(qg),
                           ordinal_base, key, ord);
     int32_t* list = col_list + (size_t)qg * col_cap;
     for (int c = tid; c < k; c += kDenseMergeThreads)
@@ -2187,6 +2247,72 @@ __global__ __launch_bounds__(kDenseMergeThreads) void dense_collect_merge_kernel
       out_rank, out_count, flags);
 }
 
+// The same for armi_dense_topk_qmask: the helpers of an overflowed query filter by that query's
+// own mask, and every query's flag word gets flag_or (ARMI_FLAG_QMASK).
+template <int DIM>
+__global__ __launch_bounds__(kDenseMergeThreads) void dense_collect_merge_qmask_kernel(
+    const int32_t* __restrict__ col_cnt, int32_t* __restrict__ col_list, int col_cap,
+    int32_t* __restrict__ help_done, int nq, const uint16_t* __restrict__ rows,
+    const double* __restrict__ inv_norm, const int64_t* __restrict__ norm2,
+    const uint64_t* __restrict__ row_masks, int64_t mask_stride,
+    const int32_t* __restrict__ q_mask, int n_masks, int64_t n_rows,
+    const uint16_t* __restrict__ queries, const double* __restrict__ inv_q, int k,
+    int64_t ordinal_base, float* __restrict__ out_scores, int64_t* __restrict__ out_ids,
+    double* __restrict__ out_rank, int32_t* __restrict__ out_count, uint32_t* __restrict__ flags,
+    uint32_t flag_or) {
+  collect_merge_body<DIM>(blockIdx.x, (int)gridDim.x - nq, col_cnt, col_list, col_cap, help_done, nq, rows,
+      inv_norm, norm2, row_masks, n_rows, queries, inv_q, k, ordinal_base, out_scores, out_ids,
+      out_rank, out_count, flags, q_mask, n_masks, mask_stride, flag_or);
+}
+
+// First kernel of armi_dense_topk_qmask: the call's mask image [n_qb][T][kQB] of u32 (see
+// scan_i8_body) from the caller's ordinal masks and q_mask. Workgroup (x, y) covers the 64
+// ordinal residues u = 64 x .. (image tile tau(u) = u * perm_mul mod T holds ordinals u + p T at its
+// rows p, armi_index.h) for kPrepQueries queries: block qb = y / 4, its columns 16 (y % 4) .. + 15.
+// A wave takes one query at a time with lane = residue, so for each p its 64 lanes test 64
+// consecutive ordinals of one mask (one or two words, the 32 loads of a word all in flight); the
+// words then turn through LDS so that each tile's 16 words leave as one 64-B run. (One workgroup
+// per 64 queries left 49 workgroups at 100k rows, each thread walking 16 x 32 loads: 0.16 ms at
+// 100k and at 1M rows alike, latency, not bytes.)
+// Bits of ordinals >= n_rows and words of queries past nq are 0; a query without a mask (-1, or an
+// entry outside [0, n_masks), which never indexes row_masks) gets every row below n_rows.
+constexpr int kPrepTiles = 64;
+constexpr int kPrepQueries = 16;
+static_assert(kQB % kPrepQueries == 0 && kPrepQueries % 4 == 0, "query groups of the prep grid");
+__global__ __launch_bounds__(256) void qmask_prep_kernel(
+    const uint64_t* __restrict__ row_masks, int64_t mask_stride, const int32_t* __restrict__ q_mask,
+    int n_masks, int nq, int64_t n_rows, int64_t T, int64_t perm_mul, uint32_t* __restrict__ out) {
+  __shared__ uint32_t words[kPrepTiles][kPrepQueries + 1];  // [residue][query], padded
+  const int lane = threadIdx.x & 63;
+  const int wave = armi::wave_id();
+  constexpr int kGroups = kQB / kPrepQueries;
+  const int qb = blockIdx.y / kGroups;
+  const int c0 = (blockIdx.y % kGroups) * kPrepQueries;  // the workgroup's first column
+  const int64_t u0 = (int64_t)blockIdx.x * kPrepTiles;
+  const int64_t u = u0 + lane;
+  for (int c = wave; c < kPrepQueries; c += 4) {
+    const int q = qb * kQB + c0 + c;
+    uint32_t w = 0;
+    if (q < nq && u < T) {
+      const int m = q_mask[q];  // (wave-uniform)
+      const uint64_t* mk = m >= 0 && m < n_masks ? row_masks + (int64_t)m * mask_stride : nullptr;
+#pragma unroll
+      for (int p = 0; p < TILE_ROWS; ++p) {
+        const int64_t i = u + p * T;
+        if (i < n_rows && (!mk || ((mk[i >> 6] >> (i & 63)) & 1ull))) w |= 1u << p;
+      }
+    }
+    words[lane][c] = w;
+  }
+  __syncthreads();
+  // thread -> (residue uu, column cc): 16 consecutive threads write one tile's 64-B run
+  for (int e = threadIdx.x; e < kPrepTiles * kPrepQueries; e += 256) {
+    const int uu = e / kPrepQueries, cc = e % kPrepQueries;
+    if (u0 + uu >= T) break;
+    const int64_t tau = ((u0 + uu) * perm_mul) % T;
+    out[((int64_t)qb * T + tau) * kQB + c0 + cc] = words[uu][cc];
+  }
+}
 
 // First kernel of a filtered int8-scan call: the caller's row filter in int8 image order: bit p
 // of the output = bit img_to_ord(p) of the caller's ordinal mask (0 for padding positions), one
@@ -2720,6 +2846,83 @@ int dense_second_pass(const armi_index* idx, const uint16_t* queries, int nq, in
   return ARMI_OK;
 }
 
+// armi_dense_topk_qmask: armi_dense_topk's int8-filter call (1-2 query blocks) with one row mask
+// per query. Five launches: the mask image, the int8 first pass, the merge (unchanged: its
+// candidates are enabled rows), the collect pass and its merge. Calls of this shape only
+// (qmask_supported); the mask image sits in front of the armi_dense_topk workspace.
+bool qmask_supported(const armi_index* idx, int nq, int k) {
+  return idx->rows8 != nullptr && nq >= 1 && nq <= 2 * kQB && k >= 1 && k <= kI8MaxK;
+}
+
+size_t qmask_img_bytes(const armi_index* idx, int nq) {
+  const size_t n_qb = (size_t)(nq + kQB - 1) / kQB;
+  return armi::align_up(n_qb * (size_t)std::max<int64_t>(idx->n_tiles, 1) * kQB * 4, 256);
+}
+
+template <int DIM>
+int dense_topk_qmask_impl(const armi_index* idx, const uint16_t* queries, int nq, int k,
+                          const uint64_t* row_masks, int64_t mask_stride, const int32_t* q_mask,
+                          int n_masks, uint32_t* mask_img, float* out_scores, int64_t* out_ids,
+                          double* out_rank, int32_t* out_count, uint32_t* out_flags,
+                          const Workspace& w, hipStream_t stream) {
+  const ScanPlan sp = plan_scan(idx, k, nq);
+  const int64_t T = std::max<int64_t>(idx->n_tiles, 1);
+  const bool nt = use_nt_stream(idx);
+  {
+    const int rc_l = armi::timed_kernel(
+        ARMI_TIMING_QMASK_PREP, qmask_prep_kernel,
+        dim3((unsigned)((T + kPrepTiles - 1) / kPrepTiles), sp.n_qb * (kQB / kPrepQueries)),
+        dim3(256), 0, stream,
+        row_masks, mask_stride, q_mask, n_masks, nq, idx->n_rows, T, idx->perm_mul, mask_img);
+    ARMI_LAUNCHED("qmask_prep_kernel");
+    if (rc_l) return rc_l;
+  }
+  {
+    auto kern = nt ? dense_scan_i8_qmask_kernel<DIM, false, true>
+                   : dense_scan_i8_qmask_kernel<DIM, false, false>;
+    if (int rc = allow_lds(kern, scan_i8_lds_bytes<DIM>())) return rc;
+    const int rc_l = armi::timed_kernel(
+        ARMI_TIMING_DENSE_SCAN, kern, dim3(scan_grid(sp.n_qb, sp.n_wg)), dim3(kThreads),
+        scan_i8_lds_bytes<DIM>(), stream, (const int8_t*)idx->rows8, (const float*)idx->a32,
+        (const float*)idx->e32, (const uint32_t*)mask_img, idx->n_rows, idx->n_tiles,
+        sp.tiles_per_wg, sp.n_wg, sp.n_qb, queries, nq, w.cand_key, w.cand_row, w.cand_bound,
+        (const int32_t*)idx->tile_ord, (const uint32_t*)nullptr, (const float*)nullptr,
+        (int32_t*)nullptr, (int32_t*)nullptr, 0);
+    ARMI_LAUNCHED("dense_scan_i8_qmask_kernel");
+    if (rc_l) return rc_l;
+  }
+  const int kc = kc_i8(k);
+  ARMI_REQUIRE(sp.n_wg >= 1 && sp.n_wg * kKW <= kMaxPool,
+               "dense merge: the candidate pool must fit one filter round (<= 256 lists)");
+  int sel_col = 1, sel_rank = kc;
+  merge_select(kc, sp.n_wg, sel_col, sel_rank);
+  dense_merge_kernel<DIM><<<dim3(nq), dim3(kDenseMergeThreads), kMergeLds, stream>>>(
+      w.cand_key, w.cand_row, w.cand_bound, sp.n_wg, nq, idx->rows, idx->inv_norm, queries,
+      w.inv_q, w.qnorm, k, kc, sel_col, sel_rank, idx->ordinal_base, out_scores, out_ids, out_rank,
+      out_count, out_flags, w.thr, w.col_cnt, w.help_done, merge_two_stage(kc) ? 1 : 0);
+  ARMI_LAUNCHED("dense_merge_kernel");
+  {
+    const ScanPlan cp = plan_scan(idx, k, 1);
+    auto kern = nt ? dense_scan_i8_qmask_kernel<DIM, true, true>
+                   : dense_scan_i8_qmask_kernel<DIM, true, false>;
+    if (int rc = allow_lds(kern, scan_i8_lds_bytes<DIM>())) return rc;
+    kern<<<dim3(scan_grid(sp.n_qb, cp.n_wg)), dim3(kThreads), scan_i8_lds_bytes<DIM>(), stream>>>(
+        idx->rows8, idx->a32, idx->e32, mask_img, idx->n_rows, idx->n_tiles, cp.tiles_per_wg,
+        cp.n_wg, sp.n_qb, queries, nq, nullptr, nullptr, nullptr, idx->tile_ord, out_flags, w.thr,
+        w.col_cnt, w.col_list, kCollectCap);
+    ARMI_LAUNCHED("dense_scan_i8_qmask_kernel(collect)");
+  }
+  if (int rc = allow_lds(dense_collect_merge_qmask_kernel<DIM>, kColMergeLds)) return rc;
+  const int n_help = std::max(1, std::min<int>(kMaxHelp, kCollectCap / k));
+  dense_collect_merge_qmask_kernel<DIM><<<dim3(nq + n_help), dim3(kDenseMergeThreads),
+                                          kColMergeLds, stream>>>(
+      w.col_cnt, w.col_list, kCollectCap, w.help_done, nq, idx->rows, idx->inv_norm, idx->norm2,
+      row_masks, mask_stride, q_mask, n_masks, idx->n_rows, queries, w.inv_q, k,
+      idx->ordinal_base, out_scores, out_ids, out_rank, out_count, out_flags, ARMI_FLAG_QMASK);
+  ARMI_LAUNCHED("dense_collect_merge_qmask_kernel");
+  return ARMI_OK;
+}
+
 
 // ------------------------------------------------------------------------------ live tail pass
 // armi_dense_tail_topk: the global top-k of a finished list over the main segment and a small
@@ -3176,6 +3379,58 @@ int armi_dense_topk(const armi_index* idx, const uint16_t* queries, int n_querie
     constexpr int DIM = decltype(D)::value;
     return dense_topk_impl<DIM>(idx, queries, n_queries, k, row_mask, out_scores, out_ids, rank,
                                 out_count, out_flags, w, stream);
+  });
+}
+
+int armi_dense_qmask_supported(const armi_index* idx, int n_queries, int k) {
+  return idx && qmask_supported(idx, n_queries, k) ? 1 : 0;
+}
+
+// Workspace layout: [mask image][armi_dense_topk's workspace for the same call]
+size_t armi_dense_qmask_workspace_bytes(const armi_index* idx, int n_queries, int k, int n_masks) {
+  if (!idx || n_masks < 0 || !qmask_supported(idx, n_queries, k)) return 0;
+  return qmask_img_bytes(idx, n_queries) + armi_dense_workspace_bytes(idx, n_queries, k);
+}
+
+int armi_dense_topk_qmask(const armi_index* idx, const uint16_t* queries, int n_queries, int k,
+                          const uint64_t* row_masks, int64_t mask_stride_words,
+                          const int32_t* q_mask, int n_masks, float* out_scores, int64_t* out_ids,
+                          double* out_rank, int32_t* out_count, uint32_t* out_flags,
+                          void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  ARMI_REQUIRE(idx != nullptr, "armi_dense_topk_qmask: index is null");
+  ARMI_REQUIRE(n_queries >= 0, "armi_dense_topk_qmask: n_queries < 0");
+  ARMI_REQUIRE(k >= 1 && k <= kMaxK, "armi_dense_topk_qmask: k must be in [1, 240]");
+  ARMI_REQUIRE(n_masks >= 0, "armi_dense_topk_qmask: n_masks < 0");
+  ARMI_REQUIRE(mask_stride_words >= (idx->n_rows + 63) / 64,
+               "armi_dense_topk_qmask: mask_stride_words < ceil(rows / 64)");
+  if (n_queries == 0) return ARMI_OK;
+  if (!qmask_supported(idx, n_queries, k))
+    return armi::fail(ARMI_ERR_UNSUPPORTED,
+                      "armi_dense_topk_qmask: needs an int8 image, n_queries <= 128 and k <= 64");
+  ARMI_REQUIRE(queries && q_mask && (row_masks || n_masks == 0) && out_scores && out_ids &&
+                   out_count && out_flags && workspace,
+               "armi_dense_topk_qmask: null pointer argument");
+  ARMI_REQUIRE(workspace_bytes >= armi_dense_qmask_workspace_bytes(idx, n_queries, k, n_masks),
+               "armi_dense_topk_qmask: workspace too small");
+  ARMI_HIP(hipSetDevice(idx->device));
+  if (idx->n_rows == 0) {
+    ARMI_HIP(hipMemsetAsync(out_count, 0, sizeof(int32_t) * n_queries, stream));
+    ARMI_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out_flags), (int)ARMI_FLAG_QMASK,
+                               n_queries, stream));
+    ARMI_HIP(hipMemsetAsync(out_ids, 0xff, sizeof(int64_t) * n_queries * k, stream));
+    return ARMI_OK;
+  }
+  char* base = static_cast<char*>(workspace);
+  uint32_t* mask_img = reinterpret_cast<uint32_t*>(base);
+  base += qmask_img_bytes(idx, n_queries);
+  const Workspace w = carve(base, idx, n_queries, k, true);
+  double* rank = out_rank;
+  if (!rank) rank = reinterpret_cast<double*>(base + armi::align_up(w.bytes, 256));
+  return dispatch_dim(idx->dim, [&](auto D) {
+    constexpr int DIM = decltype(D)::value;
+    return dense_topk_qmask_impl<DIM>(idx, queries, n_queries, k, row_masks, mask_stride_words,
+                                      q_mask, n_masks, mask_img, out_scores, out_ids, rank,
+                                      out_count, out_flags, w, stream);
   });
 }
 

@@ -9,7 +9,7 @@ submit single queries from any thread and get a Future of the reference-shaped
 list[RetrievalResult]; one worker thread drains the queue into batches of up to max_batch
 queries, waiting at most max_wait_ms after the first arrival, and runs one
 MI355XRetriever.search_batch per (filter, has-sparse) group; with the retriever's
-filter_list_rows knob on, one per has-sparse group, the requests' filters going along as
+filter_list_rows or filter_query_masks knob on, one per has-sparse group, the requests' filters going along as
 search_batch's per-query list. Per-query semantics are those of MI355XRetriever.search
 (qdrant.py:227-352); only the grouping is new.
 """
@@ -157,9 +157,9 @@ class QueryBatcher:
             if first is None:
                 break
             batch, stop = self._collect(first)
-            # with the retriever's filter_list_rows knob on, a batch keeps its queries' own
-            # filters (search_batch's list form: its planner groups them); off, one search per
-            # filter as before
+            # with the retriever's filter_list_rows or filter_query_masks knob on, a batch keeps
+            # its queries' own filters (search_batch's list form: its planner groups them); off,
+            # one search per filter as before
             mixed = self._mixed_filters()
             groups: dict = {}
             for r in batch:
@@ -180,7 +180,7 @@ class QueryBatcher:
 
     def _mixed_filters(self) -> bool:
         r = self.retriever
-        return r.config.filter_list_rows > 0 and r._world == 1
+        return (r.config.filter_list_rows > 0 or r.config.filter_query_masks) and r._world == 1
 
     def _serve(self, reqs: list[_Request]) -> None:
         try:

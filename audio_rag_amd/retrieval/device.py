@@ -120,6 +120,30 @@ def _check_row_lists(list_ptr: torch.Tensor, list_rows: torch.Tensor, q_list: to
     return n_lists
 
 
+def _check_row_masks(row_masks: torch.Tensor, q_mask: torch.Tensor, n_queries: int,
+                     n_rows: int) -> tuple[int, int]:
+    """Argument checks of DenseIndex.topk_masks (include/armi.h, armi_dense_topk_qmask); returns
+    (n_masks, stride in words). q_mask is checked for its range only when it lives on the host (a
+    device q_mask is not read back: that would synchronise every call; the kernels treat an entry
+    outside [-1, n_masks) as -1)."""
+    need = (n_rows + 63) // 64
+    if not isinstance(row_masks, torch.Tensor) or row_masks.dtype != torch.int64 or \
+            row_masks.dim() != 2 or not row_masks.is_cuda or not row_masks.is_contiguous():
+        raise ValueError("row_masks must be a contiguous 2-D int64 device tensor [n_masks, words]")
+    n_masks, stride = int(row_masks.shape[0]), int(row_masks.shape[1])
+    if stride < need:
+        raise ValueError(f"row_masks rows must hold >= {need} words")
+    if not isinstance(q_mask, torch.Tensor) or q_mask.dtype != torch.int32 or q_mask.dim() != 1 \
+            or not q_mask.is_contiguous():
+        raise ValueError("q_mask must be a contiguous 1-D int32 tensor")
+    if int(q_mask.numel()) != n_queries:
+        raise ValueError(f"q_mask names {q_mask.numel()} masks for {n_queries} queries")
+    if not q_mask.is_cuda and n_queries and not (-1 <= int(q_mask.min()) and
+                                                 int(q_mask.max()) < n_masks):
+        raise ValueError(f"q_mask entries must be in [-1, {n_masks})")
+    return n_masks, stride
+
+
 def _on_device(t: torch.Tensor, device: torch.device) -> torch.Tensor:
     return t if t.is_cuda else t.to(device)
 
@@ -225,6 +249,38 @@ class DenseIndex:
             call("armi_dense_topk", self._handle, ptr(queries), b, k, ptr(row_mask),
                  ptr(out.scores), ptr(out.ids), ptr(out.rank), ptr(out.count), ptr(out.flags),
                  ptr(workspace), workspace.numel(), s)
+        return out
+
+    def qmask_supported(self, n_queries: int, k: int) -> bool:
+        """Whether topk_masks answers this call shape (an int8 image, <= 128 queries, k <= 64)."""
+        return int(query("armi_dense_qmask_supported", self._handle, n_queries, k)) == 1
+
+    def qmask_workspace_bytes(self, n_queries: int, k: int, n_masks: int) -> int:
+        return int(query("armi_dense_qmask_workspace_bytes", self._handle, n_queries, k, n_masks))
+
+    def topk_masks(self, queries: torch.Tensor, k: int, row_masks: torch.Tensor,
+                   q_mask: torch.Tensor, workspace: torch.Tensor | None = None,
+                   out: TopK | None = None) -> TopK:
+        """Cosine top-k of every query under its own row mask, one pass over the int8 image per
+        64 queries (armi_dense_topk_qmask): row_masks int64 [n_masks, words] device bitmasks
+        (topk's row_mask convention, one per row of the tensor), q_mask int32 [B] the mask of each
+        query or -1 for none (a host tensor is uploaded). The same ranking, scores and rank keys
+        as topk(row_mask=...) called once per mask; flags carry ARMI_FLAG_QMASK. A call shape
+        outside qmask_supported() raises ArmiError (ARMI_ERR_UNSUPPORTED)."""
+        _check_fp16_2d(queries, "queries", self.dim)
+        _check_k(k)
+        b = int(queries.shape[0])
+        dev = self.device
+        n_masks, stride = _check_row_masks(row_masks, q_mask, b, self.n_rows)
+        q_mask = _on_device(q_mask, dev)
+        if out is None:
+            out = TopK.empty(b, k, dev, rank=True)
+        if b == 0:
+            return out
+        workspace = _workspace(workspace, self.qmask_workspace_bytes(b, k, n_masks), dev)
+        call("armi_dense_topk_qmask", self._handle, ptr(queries), b, k, ptr(row_masks), stride,
+             ptr(q_mask), n_masks, ptr(out.scores), ptr(out.ids), ptr(out.rank), ptr(out.count),
+             ptr(out.flags), ptr(workspace), workspace.numel(), stream_handle())
         return out
 
     def rowlist_workspace_bytes(self, n_queries: int, k: int, max_list_rows: int) -> int:

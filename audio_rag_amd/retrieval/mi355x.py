@@ -88,9 +88,17 @@ class FilterGroup:
     queries: list
     matches: int = -1       # rows the filter matches (-1: not counted, the knob is off / no filter)
     rowlist: bool = False   # ranked from the matching rows (armi_*_rowlist_topk), else a masked scan
+    qmask: bool = False     # its masked dense scan is shared with the other qmask groups of the
+    #                         call (armi_dense_topk_qmask), else a masked search of its own
 
 
-def plan_filter_groups(filters: list, n_rows: int, knob: int, count_matches) -> list[FilterGroup]:
+QMASK_MODES = ("dense", "legacy_dense", "hybrid")
+QMASK_MAX_QUERIES = 128  # queries of one armi_dense_topk_qmask call
+
+
+def plan_filter_groups(filters: list, n_rows: int, knob: int, count_matches,
+                       query_masks: bool = False, mode: str = "dense", tail_rows: int = 0,
+                       qmask_supported=None) -> list[FilterGroup]:
     """Groups the queries of a batch by filter (in order of first appearance) and picks each
     group's path. A group of q queries whose filter matches m of the collection's n_rows rows is
     ranked from its row list iff the knob is on (filter_list_rows > 0), m <= knob and
@@ -99,7 +107,15 @@ def plan_filter_groups(filters: list, n_rows: int, knob: int, count_matches) -> 
     int8 image, once per pass of up to 64 queries), so a chosen list never reads more than the scan
     it replaces. An empty match list always qualifies (count 0). Queries without a filter, and
     every group the rule refuses, take the masked scan. count_matches(filter) -> m is asked only
-    with the knob on. For a live collection m and n_rows count both segments."""
+    with the knob on. For a live collection m and n_rows count both segments.
+
+    Then the groups left to the masked scan, the unfiltered one included, are marked `qmask`:
+    their dense scans become one scan of the int8 image per 64 queries in which every query
+    carries its own mask (DenseIndex.topk_masks). All of: query_masks (the filter_query_masks knob)
+    on, at least two such groups (one group is one masked search already), mode dense /
+    legacy_dense / hybrid (the sparse kernels have no such form), no tail rows (nor has the live
+    tail pass) and qmask_supported(queries of a call) -> bool (the dense index's answer for the
+    leg's k: an int8 image, k <= 64). Otherwise they stay one masked search per group."""
     groups: dict = {}
     for i, f in enumerate(filters):
         g = groups.get(filter_key(f))
@@ -110,7 +126,38 @@ def plan_filter_groups(filters: list, n_rows: int, knob: int, count_matches) -> 
         if knob > 0 and g.filter:
             g.matches = int(count_matches(g.filter))
             g.rowlist = g.matches <= knob and 2 * len(g.queries) * g.matches <= n_rows
+    rest = [g for g in groups.values() if not g.rowlist]
+    if query_masks and len(rest) >= 2 and mode in QMASK_MODES and tail_rows == 0 and \
+            qmask_supported is not None:
+        n = sum(len(g.queries) for g in rest)
+        if qmask_supported(min(n, QMASK_MAX_QUERIES)):
+            for g in rest:
+                g.qmask = True
     return list(groups.values())
+
+
+def qmask_calls(groups: list[FilterGroup], limit: int = QMASK_MAX_QUERIES) -> list[tuple]:
+    """The topk_masks calls that serve the qmask groups of a plan: their queries in the groups'
+    order, cut into calls of at most `limit`; per call (query indexes, filters, q_mask): the
+    distinct filters of the call's queries in order of first appearance (the rows of the stacked
+    mask tensor) and, per query, its filter's row or -1 for no filter. Queries that repeat a
+    filter share its row."""
+    pairs = [(i, g.filter) for g in groups if g.qmask for i in g.queries]
+    calls = []
+    for lo in range(0, len(pairs), limit):
+        rows: dict = {}
+        filters, q_mask = [], []
+        for _, f in pairs[lo:lo + limit]:
+            if not f:
+                q_mask.append(-1)
+                continue
+            key = filter_key(f)
+            if key not in rows:
+                rows[key] = len(filters)
+                filters.append(f)
+            q_mask.append(rows[key])
+        calls.append(([i for i, _ in pairs[lo:lo + limit]], filters, q_mask))
+    return calls
 
 
 def fp16_rows(vectors: list[list[float]] | np.ndarray, dim: int) -> np.ndarray:
@@ -371,8 +418,10 @@ class MI355XRetriever(BaseRetriever):
         filter for every query, or a list of one `dict | None` per query (the reference's API
         takes one filter per request, api/v1/query.py:41). With config.filter_list_rows > 0 the
         queries are grouped by filter and selective groups are ranked from their matching rows
-        (plan_filter_groups); the answers do not depend on the path, only TopK.flags tell
-        (ARMI_FLAG_ROWLIST). With num_gpus > 1 the knob is ignored and the list form refused."""
+        (plan_filter_groups); with config.filter_query_masks the groups left to the masked scan
+        share one dense scan per 64 queries, each query under its own mask. The answers do not
+        depend on the path, only TopK.flags tell (ARMI_FLAG_ROWLIST, ARMI_FLAG_QMASK). With
+        num_gpus > 1 the knobs are ignored and the list form refused."""
         resolved = self._ensure_collection(collection_name)
         top_k = top_k or self.config.top_k
         search_type = search_type or self.config.search_type
@@ -397,17 +446,23 @@ class MI355XRetriever(BaseRetriever):
     def _search_planned(self, coll: ChunkCollection, queries: QueryBatch, top_k: int, mode: str,
                         filters: list) -> TopK:
         """search_batch with one filter per query: the planner's groups (plan_filter_groups), all
-        row-list groups in one dense and one sparse launch per segment, every other group by
-        today's masked search, one call per group; the results scattered back in query order with
-        their flags (ARMI_FLAG_ROWLIST on the row-list queries)."""
+        row-list groups in one dense and one sparse launch per segment, the qmask groups in one
+        dense scan per 64 queries (_search_qmask), every other group by the masked search, one
+        call per group; the results scattered back in query order with their flags
+        (ARMI_FLAG_ROWLIST on the row-list queries, ARMI_FLAG_QMASK from the kernel)."""
         from audio_rag_amd._armi import ARMI_FLAG_ROWLIST
 
         seg = coll.segments()
         b = int(queries.dense.shape[0])
         knob = self.config.filter_list_rows
-        n_rows = seg.dense.n_rows + (seg.tail.n_rows if seg.tail is not None else 0)
+        tail_rows = seg.tail.n_rows if seg.tail is not None else 0
+        n_rows = seg.dense.n_rows + tail_rows
+        leg_k = 2 * top_k if mode == "hybrid" else top_k
         groups = plan_filter_groups(filters, n_rows, knob,
-                                    lambda f: coll.segment_row_lists(f, knob)[2])
+                                    lambda f: coll.segment_row_lists(f, knob)[2],
+                                    query_masks=self.config.filter_query_masks, mode=mode,
+                                    tail_rows=tail_rows,
+                                    qmask_supported=lambda n: seg.dense.qmask_supported(n, leg_k))
         self.last_plan = groups
         if len(groups) == 1 and not groups[0].rowlist:  # one masked search, as without a plan
             return self._search_device(coll, queries, top_k, mode,
@@ -419,8 +474,11 @@ class MI355XRetriever(BaseRetriever):
             out = self._search_rowlists(seg, self._select(queries, idx), top_k, mode,
                                         *self._encode_rowlists(coll, listed))
             parts.append((idx, out, ARMI_FLAG_ROWLIST))
+        for idx, flt, q_mask in qmask_calls(groups):
+            out = self._search_qmask(coll, seg, self._select(queries, idx), top_k, mode, flt, q_mask)
+            parts.append((idx, out, 0))
         for g in groups:
-            if not g.rowlist:
+            if not g.rowlist and not g.qmask:
                 out = self._search_device(coll, self._select(queries, g.queries), top_k, mode,
                                           coll.segment_masks(g.filter))
                 parts.append((g.queries, out, 0))
@@ -517,6 +575,43 @@ class MI355XRetriever(BaseRetriever):
         if mode == "sparse":
             return sparse(top_k)
         return dense(top_k)
+
+    def _search_qmask(self, coll: ChunkCollection, seg, queries: QueryBatch, top_k: int, mode: str,
+                      filters: list, q_mask: list) -> TopK:
+        """One qmask_calls call (<= 128 queries, in that call's order): the dense leg is one
+        DenseIndex.topk_masks over the stacked masks of `filters`; hybrid's sparse leg stays one
+        masked SparseIndex.topk per distinct filter, scattered into the call's order, and one RRF
+        fuses the two legs for the whole call (RRF is per query). No tail rows (the planner)."""
+        dev = self.device
+        masks = [coll.filter_mask(f) for f in filters]
+        words = max((seg.dense.n_rows + 63) // 64, 1)
+        stacked = torch.stack(masks) if masks else torch.empty((0, words), dtype=torch.int64,
+                                                               device=dev)
+        qm = torch.tensor(q_mask, dtype=torch.int32, device=dev)
+
+        def dense(k: int) -> TopK:
+            return seg.dense.topk_masks(queries.dense, k, stacked, qm)
+
+        if mode != "hybrid":
+            return dense(top_k)
+        by_mask: dict = {}
+        for i, m in enumerate(q_mask):
+            by_mask.setdefault(m, []).append(i)
+
+        def sparse(k: int) -> TopK:
+            parts = []
+            for m, idx in by_mask.items():
+                sub = self._select(queries, idx)
+                s = seg.sparse.topk(sub.sparse_indptr, sub.sparse_indices, sub.sparse_values, k,
+                                    row_mask=None if m < 0 else masks[m])
+                parts.append((idx, s, 0))
+            return self._scatter(parts, len(q_mask))
+
+        if self._hybrid is None:
+            self._hybrid = ConcurrentHybrid(self.device)
+        sq = (queries.sparse_indptr, queries.sparse_indices, queries.sparse_values)
+        return self._hybrid(lambda: dense(2 * top_k), lambda: sparse(2 * top_k),
+                            sq + tuple(masks), top_k, rrf_k=self.config.rrf_k)
 
     def _scatter(self, parts: list, b: int) -> TopK:
         """One TopK in query order from the groups' results: parts = (query indexes, TopK, flag

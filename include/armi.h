@@ -58,8 +58,10 @@ extern "C" {
  * must not bind this library (armi_abi_version() tells). 3: growable fp16 segments
  * (armi_index_create_tail / _append / _capacity) and armi_dense_tail_topk; nothing removed.
  * 4: row-list top-k (armi_dense_rowlist_topk, armi_sparse_rowlist_topk, ARMI_FLAG_ROWLIST);
- * nothing removed. 5: armi_sparse_tail_topk (+ _workspace_bytes, _chunk_rows); nothing removed. */
-#define ARMI_ABI_VERSION 5
+ * nothing removed. 5: armi_sparse_tail_topk (+ _workspace_bytes, _chunk_rows); nothing removed.
+ * 6: per-query row masks (armi_dense_topk_qmask, + _supported, _workspace_bytes,
+ * ARMI_FLAG_QMASK); nothing removed. */
+#define ARMI_ABI_VERSION 6
 
 /* flags written per query by the top-k entry points */
 #define ARMI_FLAG_CERTIFIED 1u /* fast path proved its top-k equal to the exact ranking */
@@ -68,6 +70,8 @@ extern "C" {
                                 * ARMI_FLAG_CERTIFIED) instead of the exact scan */
 #define ARMI_FLAG_ROWLIST 8u   /* answered by a row-list entry point (armi_*_rowlist_topk): the exact
                                 * ranking of the listed rows by construction, no certificate */
+#define ARMI_FLAG_QMASK 16u    /* answered by armi_dense_topk_qmask (one row mask per query), with
+                                * ARMI_FLAG_CERTIFIED or ARMI_FLAG_FALLBACK as armi_dense_topk */
 
 const char* armi_last_error(void);
 int armi_abi_version(void);
@@ -221,6 +225,38 @@ int armi_dense_rowlist_topk(const armi_index* index, const uint16_t* queries, in
                             int32_t* out_count, uint32_t* out_flags, void* workspace,
                             size_t workspace_bytes, hipStream_t stream);
 
+/* Cosine top-k in which every query carries its own row mask, answered by one pass over the int8
+ * image per 64 queries: the batch a server sees when it coalesces requests that each bring a
+ * payload filter of any selectivity (the reference takes one filter per request,
+ * src/audio_rag/api/v1/query.py:41, built at src/audio_rag/retrieval/qdrant.py:263-269). The
+ * result of query q is bit for bit armi_dense_topk's with row_mask = that query's mask.
+ *   row_masks          uint64 [n_masks][mask_stride_words] bitmasks over the index's rows, bit r of
+ *                      mask m = row r (armi_dense_topk's row_mask convention);
+ *                      mask_stride_words >= ceil(rows / 64). Bits past the last row are ignored.
+ *                      May be null when n_masks = 0.
+ *   q_mask             int32 [n_queries] (device): the mask of query q, or -1 for no filter. An
+ *                      entry outside [-1, n_masks) is TREATED AS -1 (the query is unfiltered); it
+ *                      never indexes row_masks. Several queries may share a mask.
+ * Supported (armi_dense_qmask_supported = 1): an index with an int8 image, 1 <= n_queries <= 128
+ * and k <= 64, i.e. the calls armi_dense_scan_form reports ARMI_SCAN_INT8_FILTER for. Anything
+ * else (a growable tail index, k > 64, more queries) returns ARMI_ERR_UNSUPPORTED and
+ * _workspace_bytes 0: callers run armi_dense_topk once per mask there. Null pointers, n_masks < 0
+ * and a short stride return ARMI_ERR_INVALID before any device work.
+ * Outputs, ranking, out_rank nullability and the -1 / -inf padding as armi_dense_topk; out_flags
+ * = ARMI_FLAG_QMASK | (ARMI_FLAG_CERTIFIED or ARMI_FLAG_FALLBACK) for every query. The call first
+ * builds a mask image of 256 B per 32-row tile and 64-query block in the workspace
+ * (_workspace_bytes accounts for it), from which the scan reads each tile's masks as one run; a
+ * clear bit turns that (row, query) score into NaN, which enters no list and no bound.
+ * No host synchronisation; graph-capture safe. */
+int armi_dense_qmask_supported(const armi_index* index, int n_queries, int k);
+size_t armi_dense_qmask_workspace_bytes(const armi_index* index, int n_queries, int k,
+                                        int n_masks);
+int armi_dense_topk_qmask(const armi_index* index, const uint16_t* queries, int n_queries, int k,
+                          const uint64_t* row_masks, int64_t mask_stride_words,
+                          const int32_t* q_mask, int n_masks, float* out_scores, int64_t* out_ids,
+                          double* out_rank, int32_t* out_count, uint32_t* out_flags,
+                          void* workspace, size_t workspace_bytes, hipStream_t stream);
+
 size_t armi_dense_exact_workspace_bytes(const armi_index* index, int n_queries, int k);
 /* Exhaustive exact scan with the same outputs and ranking as armi_dense_topk. */
 int armi_dense_exact_topk(const armi_index* index, const uint16_t* queries, int n_queries, int k,
@@ -260,13 +296,15 @@ int armi_topk_merge_shards_packed(const void* packed, int64_t shard_stride,
  * armi_dense_topk), ARMI_TIMING_SPARSE_SCAN (the dominant scan of armi_sparse_topk: the MFMA
  * filter scan when the filter runs, else sparse_scan_kernel), ARMI_TIMING_ENCODER_GEMM (the
  * cross-encoder GEMMs of armi_enc_linear_f16), ARMI_TIMING_SPARSE_STAGE (a whole
- * armi_sparse_topk call).
+ * armi_sparse_topk call), ARMI_TIMING_QMASK_PREP (the mask-image kernel of armi_dense_topk_qmask,
+ * whose scan is timed under ARMI_TIMING_DENSE_SCAN).
  * armi_scan_timing_read = armi_kernel_timing_read(ARMI_TIMING_DENSE_SCAN, ...). */
 #define ARMI_TIMING_DENSE_SCAN 0
 #define ARMI_TIMING_SPARSE_SCAN 1
 #define ARMI_TIMING_ENCODER_GEMM 2
 #define ARMI_TIMING_SPARSE_STAGE 3  /* the whole armi_sparse_topk call (every pass, every kernel) */
-#define ARMI_TIMING_SLOTS 4
+#define ARMI_TIMING_QMASK_PREP 4    /* qmask_prep_kernel of armi_dense_topk_qmask */
+#define ARMI_TIMING_SLOTS 5
 int armi_scan_timing_enable(int enable);
 int armi_scan_timing_read(double* total_ms, int64_t* launches);
 int armi_kernel_timing_read(int slot, double* total_ms, int64_t* launches);

@@ -1,0 +1,172 @@
+#!/usr/bin/env python
+"""Per-query-mask measurements (DESIGN "Broad filters in one scan"): what
+RetrievalConfig.filter_query_masks buys a batch whose queries carry different broad filters. One
+hybrid collection of --rows x --dim synthetic points (audio_rag_amd/synthetic.py) with eight
+metadata keys k0..k7 of eight values each (every filter {k_j: v} matches rows / 8), served by two
+retrievers over the same device indexes: knob off (one masked search per filter: what the code did
+before the knob) and knob on. 64-query batches, dense top-5 and hybrid 40 + 40 -> 20.
+
+  (a) 64 distinct filters of rows / 8 rows each (no group passes filter_list_rows' byte parity)
+  (b) 32 unfiltered queries and 32 under one broad filter
+  (c) one filter shared by all 64 queries (the same path on and off)
+  (d) the unfiltered step (the same path on and off)
+
+Times are host clocks around work that ends in a device synchronise: search_batch as a caller runs
+it (planner, Python and launch work included), the two retrievers alternating round by round. The
+dense legs of (a) and (b) are also replayed from HIP graphs (the GPU's time for the same kernels:
+64 / 2 masked DenseIndex.topk calls against one DenseIndex.topk_masks). For (a), the launch time of
+the qmask scan kernel and of the mask-image kernel (armi_kernel_timing_read) beside the plain masked
+int8 scan's, measured the same way. The result is merged into --out (JSON, one entry per row
+count).
+
+    python tools/filter_mask_bench.py --rows 100000 --out profiles/filter_masks.json
+"""
+
+from __future__ import annotations
+
+import argparse
+import ctypes
+import json
+import sys
+from pathlib import Path
+
+import numpy as np
+import torch
+
+sys.path.insert(0, str(Path(__file__).resolve().parent))
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+
+from filter_list_bench import B, graphed, same, step_ms  # noqa: E402
+
+from audio_rag_amd import _armi, synthetic  # noqa: E402
+from audio_rag_amd.config import RetrievalConfig  # noqa: E402
+from audio_rag_amd.retrieval.collection import ChunkCollection  # noqa: E402
+from audio_rag_amd.retrieval.device import DenseIndex, SparseIndex  # noqa: E402
+from audio_rag_amd.retrieval.mi355x import MI355XRetriever, QueryBatch  # noqa: E402
+
+KEYS = 8
+
+
+def payloads(n: int) -> list[dict]:
+    """k_j of point i = (i * (2 j + 1) + j) % 8: eight values of n / 8 rows each, per key."""
+    cols = [((np.arange(n, dtype=np.int64) * (2 * j + 1) + j) % KEYS).tolist() for j in range(KEYS)]
+    return [{"text": "", "metadata": {f"k{j}": cols[j][i] for j in range(KEYS)}} for i in range(n)]
+
+
+def kernel_ms(slot: int) -> tuple[float, int]:
+    total, launches = ctypes.c_double(), ctypes.c_int64()
+    _armi.call("armi_kernel_timing_read", slot, ctypes.byref(total), ctypes.byref(launches))
+    return total.value, launches.value
+
+
+def qmask_queries(t) -> int:
+    return 0 if t.flags is None else int(((t.flags & _armi.ARMI_FLAG_QMASK) != 0).sum())
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=100_000)
+    ap.add_argument("--dim", type=int, default=1024)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--out", default="profiles/filter_masks.json")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("filter_mask_bench needs the GPU")
+    dev = torch.device("cuda", 0)
+    n, dim = args.rows, args.dim
+    res = {"rows": n, "dim": dim, "batch": B, "steps": args.steps,
+           "device": torch.cuda.get_device_name(0), "filter_rows": n // KEYS}
+
+    dense = DenseIndex(synthetic.make_rows(0, n, dim, dev))
+    sparse = SparseIndex(*synthetic.make_sparse_rows(0, n, dev), vocab=synthetic.VOCAB)
+    coll = ChunkCollection.from_indexes("audio_rag", dense, payloads(n), sparse)
+
+    def retriever(masks: bool) -> MI355XRetriever:
+        r = MI355XRetriever(RetrievalConfig(filter_query_masks=masks, reproduce_sparse_drop=False,
+                                            query_graphs=False), dim)
+        r.attach_collection(coll)
+        return r
+
+    off, on = retriever(False), retriever(True)
+    qd = synthetic.make_queries(1, B, dim, dev, seed=9)[0]
+    qi, qx, qv = synthetic.make_sparse_queries(B, dev, seed=10)
+    qb = QueryBatch(dense=qd, sparse_indptr=qi, sparse_indices=qx, sparse_values=qv)
+    modes = {"dense": 5, "hybrid": 20}
+    broad = {"k0": 0}
+    cases = {
+        "a_64_distinct_filters": [{f"k{q // KEYS}": q % KEYS} for q in range(B)],
+        "b_half_unfiltered_half_one_filter": [None] * (B // 2) + [broad] * (B // 2),
+        "c_one_shared_filter": [broad] * B,
+        "d_unfiltered": [None] * B,
+    }
+
+    def search(r, mode, flt):
+        return r.search_batch(qb, modes[mode], filter_metadata=flt, search_type=mode)[0]
+
+    for name, flt in cases.items():
+        entry = {}
+        for mode in modes:
+            x, y = search(off, mode, flt), search(on, mode, flt)
+            entry[mode] = step_ms({"off": lambda: search(off, mode, flt),
+                                   "on": lambda: search(on, mode, flt)}, dev, args.steps,
+                                  args.warmup)
+            entry[mode]["equal"] = same(x, y, mode)
+            entry[mode]["qmask_groups"] = sum(g.qmask for g in on.last_plan)
+            if mode == "dense":
+                entry[mode]["qmask_queries"] = qmask_queries(y)
+        res[name] = entry
+
+    # the dense legs of (a) and (b) as device work only, replayed from HIP graphs
+    k = modes["dense"]
+    for name in ("a_64_distinct_filters", "b_half_unfiltered_half_one_filter"):
+        flt = cases[name]
+        distinct = []
+        for f in flt:
+            if f not in distinct:
+                distinct.append(f)
+        subs = [(qd[[i for i, qf in enumerate(flt) if qf == f]].contiguous(), coll.filter_mask(f))
+                for f in distinct]
+        ws = torch.empty(dense.workspace_bytes(B, k), dtype=torch.uint8, device=dev)
+        real = [f for f in distinct if f]
+        stacked = torch.stack([coll.filter_mask(f) for f in real])
+        qm = torch.tensor([real.index(f) if f else -1 for f in flt], dtype=torch.int32, device=dev)
+        wsq = torch.empty(dense.qmask_workspace_bytes(B, k, len(real)), dtype=torch.uint8,
+                          device=dev)
+        g_off = graphed(lambda: [dense.topk(q, k, row_mask=m, workspace=ws) for q, m in subs][-1],
+                        dev)
+        g_on = graphed(lambda: dense.topk_masks(qd, k, stacked, qm, workspace=wsq), dev)
+        if g_off is not None and g_on is not None:
+            res[name]["dense"]["graph"] = step_ms({"off": g_off, "on": g_on}, dev, args.steps,
+                                                  args.warmup)
+        if name == "a_64_distinct_filters":
+            # kernel launch times: the qmask scan and its mask image against the plain masked scan
+            one = coll.filter_mask(broad)
+            _armi.call("armi_scan_timing_enable", 1)
+            kernel_ms(_armi.TIMING_DENSE_SCAN), kernel_ms(_armi.TIMING_QMASK_PREP)
+            reps = 5 * args.steps
+            for _ in range(reps):
+                dense.topk(qd, k, row_mask=one, workspace=ws)
+            plain = kernel_ms(_armi.TIMING_DENSE_SCAN)
+            for _ in range(reps):
+                dense.topk_masks(qd, k, stacked, qm, workspace=wsq)
+            scan, prep = kernel_ms(_armi.TIMING_DENSE_SCAN), kernel_ms(_armi.TIMING_QMASK_PREP)
+            _armi.call("armi_scan_timing_enable", 0)
+            res["kernels_ms"] = {
+                "masked_int8_scan": plain[0] / max(plain[1], 1),
+                "qmask_int8_scan": scan[0] / max(scan[1], 1),
+                "qmask_prep": prep[0] / max(prep[1], 1),
+                "launches": [plain[1], scan[1], prep[1]],
+                "qmask_over_masked_scan": (scan[0] / max(scan[1], 1)) / (plain[0] / max(plain[1], 1)),
+            }
+
+    out = Path(args.out)
+    merged = json.loads(out.read_text()) if out.exists() else {}
+    merged[str(n)] = res
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text(json.dumps(merged, indent=1) + "\n")
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
