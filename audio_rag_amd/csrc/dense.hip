@@ -11,9 +11,10 @@
 //      straight from HBM into VGPRs (each corpus byte is read once and used by exactly one
 //      wave), multiplies it against up to 64 queries held in LDS with
 //      v_mfma_f32_32x32x16_f16 (fp32 accumulate), scales by the fp32 inverse norm and keeps a
-//      4-deep top list per lane and query in registers. The 16 lane lists of a query are merged
-//      in LDS by a wave bitonic sort into 16 candidates per workgroup, plus the largest score
-//      any list discarded ("bound").
+//      4-deep top list per lane and query in registers. As a wave's tiles end it folds its lists
+//      into the workgroup's running list in LDS (scan_wave_fold, no barrier); the last wave
+//      writes 16 candidates per workgroup and query, plus the largest score any list or fold
+//      discarded ("bound").
 //   2. dense_merge: one workgroup per query pools all workgroup candidates, keeps the KC best
 //      approximate scores, rescores them EXACTLY (int64 dot of the 2^24 fixed-point images),
 //      sorts by (exact key desc, ordinal asc) and certifies the answer: every discarded row has
@@ -45,6 +46,10 @@ typedef int32_t i32x16 __attribute__((ext_vector_type(16)));
 typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+typedef __attribute__((address_space(3))) void* lds_ptr_t;
+typedef __attribute__((address_space(3))) float lds_f32;
+typedef __attribute__((address_space(3))) int32_t lds_i32;
 
 constexpr int kWaves = 8;
 constexpr int kThreads = kWaves * 64;
@@ -95,43 +100,37 @@ __device__ __forceinline__ f32x16 mfma16(u32x4 a, u32x4 b, f32x16 c) {
 // this access shape ran the scan at 3.3 TB/s instead of 5.4 TB/s.
 __device__ __forceinline__ u32x4 stream_load(const u32x4* p) { return *p; }
 
-// Layout of the scans' workgroup merge scratch (scan_wg_merge): lkey / lrow [kQB][kListStride]
-// and ldisc [kQB][kDiscStride]. A query's row holds the kLaneList entries of its 2 * kWaves lane
-// lists (one wave's worth) plus one pad dword: lanes r = 0..31 write query r's row at the same
-// column, so an unpadded 64-dword stride put all 32 stores of an instruction in one bank. At dim
-// 256 the scratch is larger than the query image; sized without the padding it left the discard
-// bounds of the block's last queries past the allocation (reads of 0: a bound that certified
-// wrong lists), so the size and the pointers come from the same two strides.
-constexpr int kListSlots = 2 * kWaves;                        // lane lists per query (wave, half)
-constexpr int kListStride = kListSlots * kLaneList + 1;       // 65 dwords
-constexpr int kDiscStride = kListSlots + 1;                   // 17 dwords
-constexpr int kScanMergeScratch = kQB * kListStride * 4 * 2 + kQB * kDiscStride * 4;
-static_assert(kListSlots * kLaneList == 64, "a wave sorts one query's lane-list entries");
+// The workgroup's running candidate list of a first pass (scan_wave_fold), in LDS BEHIND the query
+// image (the other waves still read the image while an early wave folds): fkey / frow [kKW][kQB]
+// (entry-major: lane = query, so the 64 lanes of a read or write fall on 64 consecutive dwords),
+// fbound [kQB], and two control words: the next ticket and the number of finished folds.
+constexpr int kFoldList = kKW * kQB * 4;                      // one of fkey / frow
+constexpr int kFoldBytes = 2 * kFoldList + kQB * 4 + 16;      // 8,464 B
+static_assert(kFoldBytes % 16 == 0, "what follows the list stays 16-byte aligned");
 
-// LDS bytes of the scan kernel: the query fragment image, later overlaid by the merge scratch.
+// The fp16 scans' query fragment image (stage_query_frags).
 template <int DIM>
-constexpr int scan_lds_bytes() {
-  constexpr int img = (DIM / 16) * 2 * kQB * 16;
-  return img > kScanMergeScratch ? img : kScanMergeScratch;
-}
+constexpr int scan_img_bytes() { return (DIM / 16) * 2 * kQB * 16; }
+
+// LDS bytes of dense_scan_kernel: the image, then the running list.
+template <int DIM>
+constexpr int scan_lds_bytes() { return scan_img_bytes<DIM>() + kFoldBytes; }
 
 // dense_scan_i8_kernel's query image (round 6): the 64 fp16 query rows as they are in memory,
 // row q at q * (2 DIM + 16) B (the 16-B pad: the MFMA B reads of 16 lanes, queries r .. r + 15 at
 // one chunk, fall on 16 distinct 4-bank groups), copied by LDS-DMA (1-KB global_load_lds_dwordx4
-// pieces of one row, no register staging); the workgroup merge reuses the region.
+// pieces of one row, no register staging).
 template <int DIM>
 constexpr int i8_qstride() { return DIM * 2 + 16; }
 template <int DIM>
-constexpr int i8_img_bytes() {
-  constexpr int img = kQB * i8_qstride<DIM>();
-  return img > kScanMergeScratch ? img : kScanMergeScratch;
-}
-// LDS bytes of dense_scan_i8_kernel: the image, then qnorm [kQB], qsel / qthr [kQB] each (collect
-// pass) and wcnt [kWaves].
+constexpr int i8_img_bytes() { return kQB * i8_qstride<DIM>(); }
+// LDS bytes of dense_scan_i8_kernel: the image, then the running list (first pass), qnorm [kQB],
+// qsel / qthr [kQB] each (collect pass) and wcnt [kWaves].
 template <int DIM>
 constexpr int scan_i8_lds_bytes() {
-  return i8_img_bytes<DIM>() + kQB * 4 + kQB * 8 + kWaves * 4;
+  return i8_img_bytes<DIM>() + kFoldBytes + kQB * 4 + kQB * 8 + kWaves * 4;
 }
+constexpr int kLdsPerWg = 160 * 1024;
 
 // ------------------------------------------------------------- pieces shared by the dense scans
 // dense_scan_kernel, scan_i8_body and dense_tail_scan_kernel are built from the helpers below; the
@@ -267,59 +266,138 @@ __device__ __forceinline__ void lane_lists_take(const float (&x)[16], float mx, 
   }
 }
 
-// Workgroup merge of a first pass: the kListSlots lane lists of each query (lane: queries r and
-// 32 + r, lists s0 / s1, discards d0 / d1) become its kKW best candidates and the bound, the
-// largest score any list discarded, at cand_*[out_base + q]. smem: kScanMergeScratch bytes that
-// overlay the (dead) query image.
-__device__ __forceinline__ void scan_wg_merge(
-    unsigned char* smem, int wave, int lane, const float (&s0)[kLaneList],
-    const int32_t (&i0)[kLaneList], float d0, const float (&s1)[kLaneList],
-    const int32_t (&i1)[kLaneList], float d1, int nq, size_t out_base,
-    float* __restrict__ cand_key, int32_t* __restrict__ cand_row, float* __restrict__ cand_bound) {
-  const int r = lane & 31;
-  const int h = lane >> 5;
-  __syncthreads();
-  float* lkey = reinterpret_cast<float*>(smem);                                // [kQB][kListStride]
-  int32_t* lrow = reinterpret_cast<int32_t*>(smem + kQB * kListStride * 4);    // [kQB][kListStride]
-  float* ldisc = reinterpret_cast<float*>(smem + kQB * kListStride * 8);       // [kQB][kDiscStride]
-  const int slot = wave * 2 + h;
+// Compare-exchange of two candidates: a ends up with the larger key (equal keys stay).
+__device__ __forceinline__ void cand_order(float& ka, int32_t& ia, float& kb, int32_t& ib) {
+  const bool sw = kb > ka;
+  const float tk = sw ? kb : ka;
+  const int32_t ti = sw ? ib : ia;
+  kb = sw ? ka : kb;
+  ib = sw ? ia : ib;
+  ka = tk;
+  ia = ti;
+}
+
+// Bitonic merge of N (a power of two) candidates held by one lane, a bitonic sequence on entry,
+// into descending order: a fixed network, no shuffles.
+template <int N>
+__device__ __forceinline__ void cand_bitonic_merge(float (&key)[N], int32_t (&row)[N]) {
 #pragma unroll
-  for (int j = 0; j < kLaneList; ++j) {
-    lkey[r * kListStride + slot * kLaneList + j] = s0[j];
-    lrow[r * kListStride + slot * kLaneList + j] = i0[j];
-    lkey[(32 + r) * kListStride + slot * kLaneList + j] = s1[j];
-    lrow[(32 + r) * kListStride + slot * kLaneList + j] = i1[j];
+  for (int stride = N / 2; stride > 0; stride >>= 1)
+#pragma unroll
+    for (int e = 0; e < N; ++e)
+      if (!(e & stride)) cand_order(key[e], row[e], key[e + stride], row[e + stride]);
+}
+
+// The empty running list and its control words; a barrier follows before any wave folds (the
+// image phase's).
+__device__ __forceinline__ void scan_fold_init(unsigned char* fold) {
+  float* fkey = reinterpret_cast<float*>(fold);
+  int32_t* frow = reinterpret_cast<int32_t*>(fold + kFoldList);
+  float* fbound = reinterpret_cast<float*>(fold + 2 * kFoldList);
+  uint32_t* fctl = reinterpret_cast<uint32_t*>(fold + 2 * kFoldList + kQB * 4);
+  for (int e = threadIdx.x; e < kKW * kQB; e += kThreads) {
+    fkey[e] = kNegInf;
+    frow[e] = -1;
   }
-  ldisc[r * kDiscStride + slot] = d0;
-  ldisc[(32 + r) * kDiscStride + slot] = d1;
-  __syncthreads();
-  // each wave merges its kQB / kWaves queries together (interleaved shuffle chains)
-  constexpr int QW = kQB / kWaves;
-  float key[QW], b[QW];
-  int32_t row[QW];
+  if (threadIdx.x < kQB) fbound[threadIdx.x] = kNegInf;
+  if (threadIdx.x < 2) fctl[threadIdx.x] = 0u;
+}
+
+// End of a first pass, called by each wave as its tile loop ends (a wave that had no tile brings
+// empty lists): the wave folds its lane lists (lane: queries r and 32 + r, lists s0 / s1, discards
+// d0 / d1) into the workgroup's running list (scan_fold_init), and the last of the kWaves writes
+// each query's kKW best candidates and the bound, the largest score any list or fold discarded, to
+// cand_*[out_base + q]. No barrier: a wave that ends early folds while the others still stream,
+// and what follows the workgroup's last wave is one fold.
+//   1. One v_permlane32_swap per value pair gives lane l both halves of query l's lists (lane r:
+//      the s0 of lanes r and 32 + r; lane 32 + r: their s1): two sorted runs of kLaneList, merged
+//      in the lane.
+//   2. The wave takes a ticket (one lane's LDS add) and sleeps until the folds before it are done.
+//      A waiter depends only on waves that hold earlier tickets, i.e. are inside this function and
+//      wait, in turn, only for earlier ones; all kWaves are resident: the chain ends at ticket 0.
+//   3. Lane = query: z[i] = better(list[i], mine[kKW - 1 - i]) is bitonic and holds the kKW best
+//      of both; the losers and the wave's discards raise the bound (-inf entries never do, and a
+//      NaN never entered a lane list).
+// Ties between equal keys may fall to either side of the cut, whichever wave comes first: what the
+// merge's certificate uses is only that every row outside the list has key <= bound.
+__device__ __forceinline__ void scan_wave_fold(
+    unsigned char* fold, int lane, const float (&s0)[kLaneList], const int32_t (&i0)[kLaneList],
+    float d0, const float (&s1)[kLaneList], const int32_t (&i1)[kLaneList], float d1, int nq,
+    size_t out_base, float* __restrict__ cand_key, int32_t* __restrict__ cand_row,
+    float* __restrict__ cand_bound) {
+  static_assert(kQB == 64 && 2 * kLaneList <= kKW, "lane = query; a wave's entries fit the list");
+  uint32_t* fctl = reinterpret_cast<uint32_t*>(fold + 2 * kFoldList + kQB * 4);  // ticket, done
+  // the lane's column of fkey / frow [kKW][kQB] and fbound [kQB]: one opaque LDS address, so that
+  // the entries are immediate offsets from it
+  uint32_t col = (uint32_t)(uintptr_t)(lds_ptr_t)fold + 4u * (uint32_t)lane;
+  asm volatile("" : "+v"(col));
+  lds_f32* fkey = reinterpret_cast<lds_f32*>(col);
+  lds_i32* frow = reinterpret_cast<lds_i32*>(col + kFoldList);
+  lds_f32* fbound = reinterpret_cast<lds_f32*>(col + 2 * kFoldList);
+  constexpr int M = 2 * kLaneList;
+  float mk[M];
+  int32_t mr[M];
 #pragma unroll
-  for (int qq = 0; qq < QW; ++qq) {
-    const int q = wave * QW + qq;
-    key[qq] = lkey[q * kListStride + lane];
-    row[qq] = lrow[q * kListStride + lane];
-    b[qq] = (lane < kListSlots) ? ldisc[q * kDiscStride + lane] : kNegInf;
+  for (int j = 0; j < kLaneList; ++j) {  // (the second run reversed: the two form a bitonic run)
+    const auto pk = __builtin_amdgcn_permlane32_swap(__float_as_uint(s0[j]), __float_as_uint(s1[j]),
+                                                     false, false);
+    const auto pr = __builtin_amdgcn_permlane32_swap((uint32_t)i0[j], (uint32_t)i1[j], false, false);
+    mk[j] = __uint_as_float(pk[0]);
+    mr[j] = (int32_t)pr[0];
+    mk[M - 1 - j] = __uint_as_float(pk[1]);
+    mr[M - 1 - j] = (int32_t)pr[1];
   }
-  armi::wave_sort_approx_desc_n<QW>(key, row);
+  const auto pd = __builtin_amdgcn_permlane32_swap(__float_as_uint(d0), __float_as_uint(d1), false,
+                                                   false);
+  float b = fmaxf(__uint_as_float(pd[0]), __uint_as_float(pd[1]));
+  cand_bitonic_merge<M>(mk, mr);
+  // (pinned in front of the wait: sunk to its first use, the sort ran inside the wave's turn)
 #pragma unroll
-  for (int qq = 0; qq < QW; ++qq)
-    if (lane == kKW) b[qq] = fmaxf(b[qq], key[qq]);
-  armi::wave_max_all_n<QW>(b);
+  for (int j = 0; j < M; ++j) asm volatile("" : "+v"(mk[j]), "+v"(mr[j]));
+
+  uint32_t ticket = 0;
+  if (lane == 0)
+    ticket = __hip_atomic_fetch_add(&fctl[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  ticket = __builtin_amdgcn_readfirstlane(ticket);
+  while (__hip_atomic_load(&fctl[1], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != ticket)
+    __builtin_amdgcn_s_sleep(1);
+
+  float zk[kKW];
+  int32_t zr[kKW];
 #pragma unroll
-  for (int qq = 0; qq < QW; ++qq) {
-    const int q = wave * QW + qq;
-    if (q >= nq) break;
-    const size_t base = out_base + q;
-    if (lane < kKW) {
-      cand_key[base * kKW + lane] = key[qq];
-      cand_row[base * kKW + lane] = row[qq];
+  for (int i = 0; i < kKW; ++i) {
+    zk[i] = fkey[i * kQB];
+    zr[i] = frow[i * kQB];
+  }
+  b = fmaxf(b, fbound[0]);
+#pragma unroll
+  for (int i = kKW - M; i < kKW; ++i) {
+    cand_order(zk[i], zr[i], mk[kKW - 1 - i], mr[kKW - 1 - i]);
+    b = fmaxf(b, mk[kKW - 1 - i]);
+  }
+  cand_bitonic_merge<kKW>(zk, zr);
+
+  if (ticket == kWaves - 1) {  // the workgroup's last fold (wave-uniform)
+    if (lane < nq) {
+      const size_t base = out_base + lane;
+      float4* ok = reinterpret_cast<float4*>(cand_key + base * kKW);
+      int4* orow = reinterpret_cast<int4*>(cand_row + base * kKW);
+#pragma unroll
+      for (int i = 0; i < kKW / 4; ++i) {
+        ok[i] = make_float4(zk[4 * i], zk[4 * i + 1], zk[4 * i + 2], zk[4 * i + 3]);
+        orow[i] = make_int4(zr[4 * i], zr[4 * i + 1], zr[4 * i + 2], zr[4 * i + 3]);
+      }
+      cand_bound[base] = b;
     }
-    if (lane == 0) cand_bound[base] = b[qq];
+    return;
   }
+#pragma unroll
+  for (int i = 0; i < kKW; ++i) {
+    fkey[i * kQB] = zk[i];
+    frow[i * kQB] = zr[i];
+  }
+  fbound[0] = b;
+  __hip_atomic_store(&fctl[1], ticket + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
 template <int DIM>
@@ -328,7 +406,7 @@ __global__ __launch_bounds__(kThreads) void dense_scan_kernel(
     const uint64_t* __restrict__ row_mask, int64_t n_rows, int64_t n_tiles, int tiles_per_wg,
     int n_ranges, int n_qb, const uint16_t* __restrict__ queries_all, int q_stride,
     float* __restrict__ cand_key, int32_t* __restrict__ cand_row, float* __restrict__ cand_bound) {
-  static_assert(scan_lds_bytes<DIM>() >= kScanMergeScratch, "the merge overlays the query image");
+  static_assert(scan_lds_bytes<DIM>() <= kLdsPerWg, "the image and the running list behind it");
   int qb, rp;
   scan_block(blockIdx.x, n_qb, qb, rp);
   if (rp >= n_ranges) return;  // workgroup-uniform, before any barrier
@@ -361,7 +439,8 @@ __global__ __launch_bounds__(kThreads) void dense_scan_kernel(
       for (int i = 0; i < 4; ++i) buf[g][i] = stream_load(cur + 8 * g + i);
   }
 
-  // 1. Query fragment image.
+  // 1. Query fragment image (and the empty running list behind it).
+  scan_fold_init(smem + scan_img_bytes<DIM>());
   stage_query_frags<DIM>(qimg, queries, nq, [](u32x4) {});
   __syncthreads();
 
@@ -401,13 +480,12 @@ __global__ __launch_bounds__(kThreads) void dense_scan_kernel(
     }
   }
 
-  // 2. Workgroup merge (the query image is dead: overlay it).
-  scan_wg_merge(smem, wave, lane, s0, i0, d0, s1, i1, d1, nq, (size_t)rp * q_stride + q0,
-                cand_key, cand_row, cand_bound);
+  // 2. The wave's lists join the workgroup's list.
+  scan_wave_fold(smem + scan_img_bytes<DIM>(), lane, s0, i0, d0, s1, i1, d1, nq,
+                 (size_t)rp * q_stride + q0, cand_key, cand_row, cand_bound);
 }
 
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 
 // 4 int8 components (one dword) -> 4 fp16 fragments components (two dwords), exactly: the
@@ -442,7 +520,7 @@ __device__ __forceinline__ u32x4 i8_load(const u32x4* p) {
 
 // Probe builds only (-DARMI_PROBE_BUILD -DARMI_I8_STAMPS): per (workgroup, wave) s_memrealtime
 // (100 MHz, chip-wide) at kernel entry, after the query image, after the tile loop and at the
-// end of the workgroup merge, read back by armi_probe_i8_stamps (not part of the ABI).
+// end of the wave's fold, read back by armi_probe_i8_stamps (not part of the ABI).
 #if defined(ARMI_PROBE_BUILD) && defined(ARMI_I8_STAMPS)
 __device__ uint64_t g_i8_stamps[256 * kWaves * 4];
 #define I8_STAMP(slot)                                                                \
@@ -481,9 +559,7 @@ __device__ __forceinline__ void scan_i8_body(
     int col_cap, const uint32_t* __restrict__ qmask_img = nullptr){
   constexpr int GROUPS = DIM / 128;  // 128-B groups of a row: 4 chunks per lane half
   constexpr int DEPTH = GROUPS % 4 == 0 ? 4 : 2;  // groups in flight per lane
-  static_assert(i8_img_bytes<DIM>() >= kScanMergeScratch &&
-                    scan_i8_lds_bytes<DIM>() >= i8_img_bytes<DIM>(),
-                "the merge overlays the query image");
+  static_assert(scan_i8_lds_bytes<DIM>() <= kLdsPerWg, "the image and what sits behind it");
   int qb, rp;
   scan_block(bid, n_qb, qb, rp);
   if (rp >= n_ranges) return;  // workgroup-uniform, before any barrier
@@ -492,8 +568,8 @@ __device__ __forceinline__ void scan_i8_body(
   const uint16_t* __restrict__ queries = queries_all + (size_t)q0 * DIM;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int QS = i8_qstride<DIM>();  // query row stride of the image (B)
-  // behind the image (scan_i8_lds_bytes):
-  float* qnorm = reinterpret_cast<float*>(smem + (size_t)i8_img_bytes<DIM>());  // [kQB] |q| up
+  // behind the image (scan_i8_lds_bytes): the running list, then
+  float* qnorm = reinterpret_cast<float*>(smem + i8_img_bytes<DIM>() + kFoldBytes);  // [kQB] |q| up
   int32_t* qsel = reinterpret_cast<int32_t*>(qnorm + kQB);                   // [kQB] COLLECT
   float* qthr = reinterpret_cast<float*>(qsel + kQB);                        // [kQB] COLLECT
   int32_t* wcnt = reinterpret_cast<int32_t*>(qthr + kQB);                    // [kWaves]
@@ -507,11 +583,12 @@ __device__ __forceinline__ void scan_i8_body(
   // wave's first tile is t_begin + wave; the counter hands out the rest in order). Round-3 stamps
   // (profiles/r03i_i8_stamps_*): with a fixed tile-per-wave split the 8 waves of a workgroup
   // ended their loops ~32 us apart on average at 1M rows (wave speed differs by ~15 % inside a
-  // CU), and the workgroup merge waits for the last of them. An LDS atomic returns in ~100 cycles
+  // CU), and the workgroup's lists are complete only with the last of them. An LDS atomic returns in ~100 cycles
   // through lgkmcnt, so unlike a device-scope dequeue it never drains the vmcnt prefetch queue.
   int32_t* const wtile = wcnt;  // wcnt[0]: next tile offset of the workgroup (non-COLLECT)
   if constexpr (!COLLECT) {
     if (threadIdx.x == 0) wtile[0] = kWaves;  // published by the image phase's barriers
+    scan_fold_init(smem + i8_img_bytes<DIM>());  // (as is the empty running list)
   }
   if constexpr (COLLECT) {
     // this block's slice [q0, q0 + 64) of the ordered list of uncertified queries
@@ -810,9 +887,9 @@ __device__ __forceinline__ void scan_i8_body(
 
   I8_STAMP(2);
   if constexpr (COLLECT) return;
-  // 2. Workgroup merge (as dense_scan_kernel; the query image is dead: overlay it).
-  scan_wg_merge(smem, wave, lane, s0, i0, d0, s1, i1, d1, nq, (size_t)rp * q_stride + q0,
-                cand_key, cand_row, cand_bound);
+  // 2. The wave's lists join the workgroup's list (as dense_scan_kernel).
+  scan_wave_fold(smem + i8_img_bytes<DIM>(), lane, s0, i0, d0, s1, i1, d1, nq,
+                 (size_t)rp * q_stride + q0, cand_key, cand_row, cand_bound);
   I8_STAMP(3);
 }
 
@@ -2944,7 +3021,7 @@ constexpr int kTailTilesPerWg = kWaves;  // one tile per wave
 constexpr int kTailWgRows = kTailTilesPerWg * TILE_ROWS;
 
 template <int DIM>
-constexpr int tail_scan_lds_bytes() { return scan_lds_bytes<DIM>() + kQB * 8 + kWaves * kQB * 8; }
+constexpr int tail_scan_lds_bytes() { return scan_img_bytes<DIM>() + kQB * 8 + kWaves * kQB * 8; }
 
 template <int DIM>
 __global__ __launch_bounds__(kThreads) void dense_tail_scan_kernel(
@@ -2953,18 +3030,15 @@ __global__ __launch_bounds__(kThreads) void dense_tail_scan_kernel(
     const uint16_t* __restrict__ queries_all, int nq_all, int k,
     const double* __restrict__ main_rank, const int32_t* __restrict__ main_count,
     int32_t* __restrict__ wg_cnt, int32_t* __restrict__ wg_list) {
-  static_assert(tail_scan_lds_bytes<DIM>() >= scan_lds_bytes<DIM>() &&
-                    scan_lds_bytes<DIM>() >= kScanMergeScratch,
-                "the fragment image (sized as the scan's, merge scratch included)");
   const int q0 = blockIdx.y * kQB;
   const int nq = min(kQB, nq_all - q0);
   const int n_wg = gridDim.x;
   const uint16_t* __restrict__ queries = queries_all + (size_t)q0 * DIM;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   u32x4* qimg = reinterpret_cast<u32x4*>(smem);  // stage_query_frags' image
-  float* s_thr = reinterpret_cast<float*>(smem + scan_lds_bytes<DIM>());       // [kQB]
-  int* s_cnt = reinterpret_cast<int*>(smem + scan_lds_bytes<DIM>() + kQB * 4);  // [kQB]
-  int64_t* s_n2 = reinterpret_cast<int64_t*>(smem + scan_lds_bytes<DIM>() + kQB * 8);  // [kWaves][kQB]
+  float* s_thr = reinterpret_cast<float*>(smem + scan_img_bytes<DIM>());       // [kQB]
+  int* s_cnt = reinterpret_cast<int*>(smem + scan_img_bytes<DIM>() + kQB * 4);  // [kQB]
+  int64_t* s_n2 = reinterpret_cast<int64_t*>(smem + scan_img_bytes<DIM>() + kQB * 8);  // [kWaves][kQB]
 
   const int wave = armi::wave_id();
   const int lane = threadIdx.x & 63;

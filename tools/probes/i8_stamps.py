@@ -1,7 +1,9 @@
 """Phase timeline of dense_scan_i8_kernel from a probe build (-DARMI_PROBE_BUILD -DARMI_I8_STAMPS):
 per (workgroup, wave) s_memrealtime stamps at entry, after the query image, after the tile loop
-and at the end of the workgroup merge, for one 64-query launch over `--chunks` rows. Prints the
-launch's phase spans (chip-wide, 10 ns ticks -> us)."""
+and at the end of the wave's fold into the workgroup's list, for one 64-query launch over
+`--chunks` rows. Prints the launch's phase spans (chip-wide, 10 ns ticks -> us). wg_pure_merge_*
+is what a workgroup still does after its last wave's loop has ended: one fold (the whole barrier
+merge before the fold replaced it)."""
 import argparse
 import ctypes
 import json
