@@ -84,6 +84,7 @@ struct armi_sparse_index {
   // value), so a pass streams 1 B per row and term and scores upper bounds on the matrix cores;
   // the candidates are rescored exactly from the fp32 columns and the rare-value tables.
   bool filter_ok = false;        // every value >= 0 (the bound needs non-negative products)
+  bool has_zero = false;         // some value is +0.0 or -0.0: the filter certifies only k-th scores > 0
   bool filter_on = true;         // armi_sparse_index_set_filter
   float* term_scale = nullptr;   // [vocab] RU(max value of the term / 255), 0 for empty terms
   int32_t n_col8 = 0;            // terms with a u8 column: df >= rows / 32

@@ -1751,9 +1751,9 @@ int build_inverted(armi_sparse_index* idx, const int64_t* indptr, const int32_t*
   uint32_t* tmax;
   unsigned long long* n_neg;
   ARMI_HIP(tmp.alloc(&tmax, (size_t)vocab + 1));
-  ARMI_HIP(tmp.alloc(&n_neg, 1));
+  ARMI_HIP(tmp.alloc(&n_neg, 2));  // {values < 0, values == 0}
   ARMI_HIP(hipMemsetAsync(tmax, 0, ((size_t)vocab + 1) * 4, stream));
-  ARMI_HIP(hipMemsetAsync(n_neg, 0, 8, stream));
+  ARMI_HIP(hipMemsetAsync(n_neg, 0, 16, stream));
   if (nnz > 0) {
     term_max_kernel<<<grid_for(nnz, 256), 256, 0, stream>>>(
         skeys, reinterpret_cast<const int2*>(idx->post), nnz, vocab, tmax, n_neg);
@@ -1783,10 +1783,11 @@ int build_inverted(armi_sparse_index* idx, const int64_t* indptr, const int32_t*
         idx->term_scale, idx->dense8_stride, idx->dense_u8);
     ARMI_LAUNCHED("dense_u8_fill_kernel");
   }
-  unsigned long long negatives = 0;
-  ARMI_HIP(hipMemcpyAsync(&negatives, n_neg, 8, hipMemcpyDeviceToHost, stream));
+  unsigned long long counts[2] = {0, 0};
+  ARMI_HIP(hipMemcpyAsync(counts, n_neg, 16, hipMemcpyDeviceToHost, stream));
   ARMI_HIP(hipStreamSynchronize(stream));
-  idx->filter_ok = negatives == 0;
+  idx->filter_ok = counts[0] == 0;
+  idx->has_zero = counts[1] != 0;
   idx->filter_on = true;
   return ARMI_OK;
 }
@@ -2490,9 +2491,9 @@ int armi_sparse_topk(const armi_sparse_index* idx, const int32_t* q_indptr,
       ARMI_LAUNCHED("sparse_filter_scan_kernel");
       if (rc_f) return rc_f;
       sparse_filter_merge_kernel<<<dim3(nqp), dim3(256), 0, stream>>>(
-          w.cand_key, w.cand_row, w.cand_bound, idx->n_ranges, q0, k, kc, idx->ordinal_base,
-          w.felig, w.fterm, w.fw, w.fnt, idx->rare_tab, idx->dense_val, idx->dense_stride,
-          out_scores, out_ids, out_count, pflags, w.kth);
+          w.cand_key, w.cand_row, w.cand_bound, idx->has_zero ? 0.f : kNegInf, idx->n_ranges, q0, k,
+          kc, idx->ordinal_base, w.felig, w.fterm, w.fw, w.fnt, idx->rare_tab, idx->dense_val,
+          idx->dense_stride, out_scores, out_ids, out_count, pflags, w.kth);
       ARMI_LAUNCHED("sparse_filter_merge_kernel");
 #ifdef ARMI_SPARSE_PROFILE
       if (dbg & 8) {

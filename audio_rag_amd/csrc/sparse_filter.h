@@ -36,8 +36,14 @@
 //     skips certified queries and exits at once when none is left.
 //
 // Limits: an index with a negative value, a pass of more than 512 distinct terms or k > 128
-// does not use the filter (the exact scan answers), and neither does a query with a negative or
-// non-finite weight.
+// does not use the filter (the exact scan answers), and neither does a query with a negative,
+// zero or non-finite weight. Rows with key 0: a row is a result when it shares an index with the
+// query, also with score 0, but a row whose shared terms all hold the value 0 (+0.0, -0.0) has
+// key 0 like a row that shares nothing, and is in no list and in no bound. Every weight of an
+// eligible query is > 0, so such rows exist only in an index that stores a zero value
+// (has_zero, counted at build). There the merge's bound of the rows left out is at least 0:
+// a query is certified only with k rescored rows and a k-th score > 0, which every key-0 row
+// (score exactly +0) is below; a shorter list or a k-th score of 0 takes the exact scan.
 
 constexpr int kFT = 1024;                      // rows per filter tile
 constexpr int kFK = 16;                        // terms per step (one MFMA k-step)
@@ -141,21 +147,24 @@ __device__ __forceinline__ uint16_t ru_half(double p) {
 // ---------------------------------------------------------------------------- index build
 
 // tmax[t] = bit pattern of the largest value of term t (values >= 0 order as their bits;
-// -0.0 counts as 0), n_neg = values < 0. Over the postings sorted by term (sorted entry i: see
-// dense_fill): a wave reduces its runs of one term first, so only the first lane of a run issues
-// the atomic (the CSR-order form's atomics on the hot terms took 21 ms per 96M values).
+// -0.0 counts as 0), n_neg[0] = values < 0, n_neg[1] = values == 0 (+0.0 or -0.0: rows the scan
+// cannot tell from rows that share nothing, see the merge's bound). Over the postings sorted by
+// term (sorted entry i: see dense_fill): a wave reduces its runs of one term first, so only the
+// first lane of a run issues the atomic (the CSR-order form's atomics on the hot terms took 21 ms
+// per 96M values).
 __global__ void term_max_kernel(const uint32_t* __restrict__ skeys, const int2* __restrict__ post,
                                 int64_t nnz, int32_t vocab, uint32_t* __restrict__ tmax,
                                 unsigned long long* __restrict__ n_neg) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int lane = threadIdx.x & 63;
   uint32_t t = 0xffffffffu, m = 0u;
-  bool neg = false;
+  bool neg = false, zero = false;
   if (i < nnz) {
     t = skeys[i];
     if (t < (uint32_t)vocab) {
       const float v = __int_as_float(post[i + t].y);
       neg = v < 0.f;
+      zero = v == 0.f;
       m = v > 0.f ? __float_as_uint(v) : 0u;
     } else {
       t = 0xffffffffu;
@@ -170,6 +179,8 @@ __global__ void term_max_kernel(const uint32_t* __restrict__ skeys, const int2* 
   if ((lane == 0 || tp != t) && t != 0xffffffffu && m) atomicMax(&tmax[t], m);
   const unsigned long long b = __ballot(neg);
   if (lane == 0 && b) atomicAdd(n_neg, (unsigned long long)__popcll(b));
+  const unsigned long long z = __ballot(zero);
+  if (lane == 0 && z) atomicAdd(n_neg + 1, (unsigned long long)__popcll(z));
 }
 
 // s_t = the least fp32 >= max_t / 255 with 255 s_t >= max_t (checked in fp64)
@@ -340,7 +351,9 @@ __device__ __forceinline__ uint32_t rare_value(const uint2* __restrict__ tab, in
 // The tail of the pass_terms block (1024 threads, after its lists are written and a barrier):
 // the pass's B slices fB[seg][q][16] (fp16 bits), scale_up, and per query whether the filter
 // may answer it (felig). A query is eligible when the pass has at most 512 distinct terms and
-// every weight of the query is finite and >= 0. A slot whose list the pass_terms wave holds in
+// every weight of the query is finite and > 0 (a weight of +0.0 or -0.0 gives B = 0: the rows
+// that share only that term would have key 0, which the scan cannot tell from sharing nothing,
+// yet they are results with score 0). A slot whose list the pass_terms wave holds in
 // registers (cap.regs: <= 64 entries, entry j in lane j) is read from there, the others from the
 // lists in global memory; one barrier (the pass's largest w * s for the exponent e).
 __device__ __forceinline__ void filter_prep_block(int nU, const QTerm* __restrict__ ql,
@@ -367,14 +380,14 @@ __device__ __forceinline__ void filter_prep_block(int nU, const QTerm* __restric
     double m = 0.0;
     if (cap.regs[i]) {  // uniform
       if (lane < n) {
-        bad = !(cap.w[i] >= 0.f) || !isfinite(cap.w[i]);  // NaN fails w >= 0
+        bad = !(cap.w[i] > 0.f) || !isfinite(cap.w[i]);  // NaN, +0.0 and -0.0 fail w > 0
         m = (double)cap.w[i] * (double)cap.s[i];
       }
     } else {
       for (int j = lane; j < n; j += 64) {
         const float w = ql[slot * kQStride + j].w;
         const float sc = fs[slot * kQStride + j];
-        bad |= !(w >= 0.f) || !isfinite(w);
+        bad |= !(w > 0.f) || !isfinite(w);
         m = fmax(m, (double)w * (double)sc);
       }
     }
@@ -794,16 +807,18 @@ __global__ __launch_bounds__(kFThreads) void sparse_filter_scan_kernel(
 // of every row left out (the lists' bounds, the pool keys below the threshold, the (kc+1)-th key).
 // Round 2 (when round 1 cannot certify): every pool entry whose key reaches round 1's k-th exact
 // score, rescored and ranked again: a row outside it has key < that score <= the true k-th, so
-// only the lists' bounds and the pool keys below it remain. (Round 2 certifies the queries whose
-// scores crowd the top, e.g. two terms present in every row: ~100 rows within the keys' slack of
-// the 40th score.) Certified queries are answered and flagged (CERTIFIED | FILTERED) with
+// only the lists' bounds and the pool keys below it remain. With fewer than k rescored rows the
+// query is certified only when nothing was left out at all (every bound -inf; never in an index
+// that stores a zero value, where the bound is at least bound_floor = 0). (Round 2 certifies the
+// queries whose scores crowd the top, e.g. two terms present in every row: ~100 rows within the
+// keys' slack of the 40th score.) Certified queries are answered and flagged (CERTIFIED | FILTERED) with
 // kth = +inf, so the exact scan and its collect pass skip them; the others are left to it.
 // Rankings are rank counts (each entry counts the entries better than it, split over 2 or 4
 // threads when few: 16-B LDS reads, no barrier per stage) instead of bitonic sorts. The query's
 // terms come from the pass_terms block's per-query table (fterm / fw / fnt).
 __global__ __launch_bounds__(256) void sparse_filter_merge_kernel(
     const float* __restrict__ cand_key, const int32_t* __restrict__ cand_row,
-    const float* __restrict__ cand_bound, int n_wg, int q_first, int k, int kc,
+    const float* __restrict__ cand_bound, float bound_floor, int n_wg, int q_first, int k, int kc,
     int64_t ordinal_base, const int32_t* __restrict__ felig, const int4* __restrict__ fterm,
     const float* __restrict__ fw, const int32_t* __restrict__ fnt,
     const uint2* __restrict__ rare_tab,
@@ -896,7 +911,10 @@ __global__ __launch_bounds__(256) void sparse_filter_merge_kernel(
   __syncthreads();
   const bool rare = sh[3] > 0;  // terms without an fp32 column: values from their postings
   ARMI_FP_T(ts[1]);
-  const float list_bound = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  // (bound_floor: 0 for an index that stores a zero value, whose key-0 rows are results the scan
+  // put in no list and no bound; -inf otherwise)
+  const float list_bound =
+      fmaxf(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])), bound_floor);
   if (wave == 0) {  // t0 = kc-th largest list maximum (one-wave radix select)
     uint32_t u[4];
 #pragma unroll

@@ -404,13 +404,18 @@ size_t armi_sparse_workspace_bytes(const armi_sparse_index* index, int n_queries
  * the collecting rescan, or, when more than 4096 rows reach its threshold, from an exact
  * term-at-a-time rescoring of the shard by helper workgroups: exact either way). score = sum
  * over shared indices, ascending index order, of fl32(q*d) accumulated in fp32 (mul and add
- * rounded separately). Only rows that share at least one index with the query are results.
- * Ranking (score desc, ordinal asc).
- * When every value of the index is >= 0 and k <= 128, a pass of at most 512 distinct terms is
- * first answered by the MFMA filter (upper bounds of every row's score from u8 levels on the
- * matrix cores, exact rescore of the best candidates, certificate): such
+ * rounded separately). Only rows that share at least one index with the query are results, and
+ * every such row is one, also when its score is 0 or negative. Ranking (score desc, ordinal asc).
+ * When every value of the index is >= 0 (-0.0 included) and k <= 128, a pass of at most 512
+ * distinct terms is first answered by the MFMA filter (upper bounds of every row's score from u8
+ * levels on the matrix cores, exact rescore of the best candidates, certificate): such
  * queries get ARMI_FLAG_CERTIFIED | ARMI_FLAG_FILTERED; the exact scan answers the rest. The
- * results are the same either way. */
+ * filter is eligible for a query whose every weight is finite and > 0: a weight of +0.0, -0.0,
+ * below 0 or NaN / inf sends the query to the exact scan. A row whose shared terms all hold the
+ * value 0 has an upper bound of 0, like a row that shares nothing, so in an index that stores a
+ * zero value (+0.0 or -0.0, found at build time) the filter certifies a query only when it has k
+ * rescored rows and the k-th score is > 0; a shorter list, or one that ends in zero scores,
+ * comes from the exact scan. The results are the same either way. */
 int armi_sparse_topk(const armi_sparse_index* index, const int32_t* q_indptr,
                      const int32_t* q_indices, const float* q_values, int n_queries, int k,
                      const uint64_t* row_mask, float* out_scores, int64_t* out_ids,

@@ -279,8 +279,10 @@ def test_sparse_rows_query_counts(gpu, oracle_mod, sparse, nq):
 
 def test_sparse_rows_zero_and_negative_scores_are_results(gpu, oracle_mod):
     """Hand-made postings: a zero-valued posting and a zero query weight leave fewer than k rows
-    with a positive score; rows that share a term rank with score 0 or below. Oracle only (the
-    MFMA filter has a known finding on zero-valued postings)."""
+    with a positive score; rows that share a term rank with score 0 or below. Against the oracle
+    and against idx.topk under the equivalent mask: first an index whose negative value keeps the
+    MFMA filter off, then the same rows with that value positive, where the filter is usable and
+    has to leave these queries (a zero weight, zero-valued postings) to the exact scan."""
     from audio_rag_amd.retrieval.device import SparseIndex
 
     rows = [([7, 9], [0.5, 0.25]),      # 0: positive
@@ -293,18 +295,32 @@ def test_sparse_rows_zero_and_negative_scores_are_results(gpu, oracle_mod):
     ip = np.concatenate([[0], np.cumsum([len(r[0]) for r in rows])]).astype(np.int64)
     ix = np.concatenate([r[0] for r in rows]).astype(np.int32)
     iv = np.concatenate([r[1] for r in rows]).astype(np.float32)
-    queries = (np.array([0, 3, 3], np.int32), np.array([7, 9, 11], np.int32),
-               np.array([0.2, 0.1, 0.0], np.float32))
+    queries = (np.array([0, 3, 3, 4], np.int32), np.array([7, 9, 11, 7], np.int32),
+               np.array([0.2, 0.1, 0.0, 0.2], np.float32))  # (query 2: the second index only)
     idx = SparseIndex(_dev(ip, gpu), _dev(ix, gpu), _dev(iv, gpu), 64, ordinal_base=BASE)
     lists = [np.arange(7, dtype=np.int32), np.array([1, 2, 3, 4], np.int32)]
     got = _check_sparse(oracle_mod, gpu, (ip, ix, iv), queries, idx, 6, lists,
-                        np.array([0, 0], np.int32), masked=False, n=7)
+                        np.array([0, 0], np.int32), n=7)
     assert got["ids"][0, :5].tolist() == [BASE + 0, BASE + 6, BASE + 1, BASE + 2, BASE + 5]
     assert got["count"].tolist() == [5, 0] and got["scores"][0, 4] < 0
     assert got["scores"][0, 2] == 0 and got["scores"][0, 3] == 0
     got = _check_sparse(oracle_mod, gpu, (ip, ix, iv), queries, idx, 6, lists,
-                        np.array([1, 1], np.int32), masked=False, n=7)
+                        np.array([1, 1], np.int32), n=7)
     assert got["ids"][0, :2].tolist() == [BASE + 1, BASE + 2] and got["count"].tolist() == [2, 0]
+    assert not idx.set_filter(True)  # (a negative value: not usable)
+    iv = np.abs(iv)  # row 5 scores 0.075: behind rows 0 and 6, before the zero-score rows
+    idx = SparseIndex(_dev(ip, gpu), _dev(ix, gpu), _dev(iv, gpu), 64, ordinal_base=BASE)
+    assert idx.set_filter(True)
+    # query 2 (term 7 alone, weight 0.2) is one the filter may answer: rows 0, 6 and the
+    # zero-valued posting of row 1
+    for l, want, want2 in ((0, [0, 6, 5, 1, 2], [0, 6, 1]), (1, [1, 2], [1])):
+        got = _check_sparse(oracle_mod, gpu, (ip, ix, iv), queries, idx, 6, lists,
+                            np.full(3, l, np.int32), n=7)
+        assert got["ids"][0, :len(want)].tolist() == [BASE + r for r in want]
+        assert got["ids"][2, :len(want2)].tolist() == [BASE + r for r in want2]
+        assert got["count"].tolist() == [len(want), 0, len(want2)]
+        assert (got["scores"][0, len(want) - 2:len(want)].view(np.uint32) == 0).all()  # +0.0
+        assert got["scores"][2, len(want2) - 1:len(want2)].view(np.uint32)[0] == 0
 
 
 def test_sparse_rows_negative_values(gpu, oracle_mod):
