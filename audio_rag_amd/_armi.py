@@ -120,6 +120,9 @@ SIGNATURES: dict[str, tuple] = {
     "armi_sparse_index_set_filter": (c_int, [c_void_p, c_int, c_void_p]),
     "armi_sparse_topk": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "armi_sparse_topk_qmask": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                       c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_size_t, c_void_p]),
     "armi_rrf_fuse": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                               c_void_p, c_void_p, c_void_p, c_void_p]),
     "armi_enc_layernorm_residual": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,

@@ -78,12 +78,21 @@ class RetrievalConfig(BaseModel):
     # different filters (or none) share one dense scan of the int8 image per 64 queries, each query
     # under its own row mask (armi_dense_topk_qmask), instead of one masked search per filter.
     # Applies to the groups filter_list_rows leaves to the masked scan when there are at least two
-    # of them, in dense and hybrid search (hybrid's sparse leg stays one search per filter), for a
-    # dense k <= 64 (hybrid: 2 * top_k), up to 128 queries per scan and a collection without tail
-    # rows; everything else (the sparse kernels, the fp16 scan of k > 64, the live tail pass, the
-    # native StreamServer) keeps one search per filter. False: as before. Answers are the same
-    # either way. Ignored with num_gpus > 1
+    # of them, in dense and hybrid search (hybrid's sparse leg stays one search per filter unless
+    # filter_query_masks_sparse is on too), for a dense k <= 64 (hybrid: 2 * top_k), up to 128
+    # queries per scan and a collection without tail rows; everything else (the fp16 scan of
+    # k > 64, the live tail pass, the native StreamServer) keeps one search per filter. False: as
+    # before. Answers are the same either way. Ignored with num_gpus > 1
     filter_query_masks: bool = False
+    # the same for the sparse kernels: True lets those groups share one sparse search per call of
+    # up to 128 queries, each query under its own row mask (armi_sparse_topk_qmask, any k): in
+    # sparse search on its own (at least two such groups, no tail rows), and for hybrid's sparse
+    # leg when filter_query_masks has put the groups into one dense scan. A knob of its own
+    # because filter_query_masks alone keeps sparse search and hybrid's sparse leg as they were.
+    # Collections with tail rows (armi_sparse_tail_topk) and the native StreamServer keep one
+    # search per filter. False: as before. Answers are the same either way. Ignored with
+    # num_gpus > 1
+    filter_query_masks_sparse: bool = False
 
 
 class RerankingConfig(BaseModel):

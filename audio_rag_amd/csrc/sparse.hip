@@ -34,6 +34,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <limits>
+#include <type_traits>
 #include <vector>
 
 #include "armi_index.h"
@@ -667,6 +668,22 @@ __device__ __forceinline__ int2 range_cursor(int32_t t, int g, int64_t lo, int n
   return make_int2(c, post[c].x);
 }
 
+// One row mask per query (armi_sparse_topk_qmask): query q of the pass (q_mask already points at
+// the pass's first query) is filtered by row q_mask[q] of the caller's [n_masks][stride] stack of
+// ordinal bitmasks; -1, and any value outside [0, n_masks), is unfiltered and indexes nothing.
+struct QMask {
+  const int32_t* q_mask;
+  int64_t stride;
+  int n_masks;
+  int nq;  // queries of the pass
+};
+__device__ __forceinline__ const uint64_t* qmask_row(const uint64_t* __restrict__ row_masks,
+                                                      const QMask& qm, int q) {
+  if (q < 0 || q >= qm.nq) return nullptr;
+  const int32_t m = qm.q_mask[q];
+  return m >= 0 && m < qm.n_masks ? row_masks + (size_t)m * qm.stride : nullptr;
+}
+
 // Workgroup = one row range; steps = (256-row tile, segment of kU = 64 pass terms). Staging: term
 // u_local of the segment is held by wave u_local & 15 (lane slot u_local >> 4), which keeps its
 // cursor, loads the term's next 128 postings (lane-reversed: postings c + 2 (63 - l) and + 1 in
@@ -679,12 +696,16 @@ __device__ __forceinline__ int2 range_cursor(int32_t t, int g, int64_t lo, int n
 // lane): the per-term list entry, address add and LDS read serve four rows instead of two. Staging of step s+1 is issued
 // before, and written after, the compute of step s (double-buffered LDS, one barrier per step).
 // kCollect = false: per-range candidate lists; kCollect = true: every row scoring >= thr.
-template <bool kCollect>
-__global__ __launch_bounds__(kScanThreads) void sparse_scan_kernel(
+// kQM = true (the *_qmask_kernel instances): row_mask is the caller's [n_masks][stride] stack and
+// query q of the pass is filtered by its own row of it (qm, see QMask); the words of the wave's
+// four queries are loaded where the shared word is, and candidates() tests each query's own bits.
+template <bool kCollect, bool kQM>
+__device__ __forceinline__ void sparse_scan_body(
     const int32_t* __restrict__ term_ptr, const int2* __restrict__ post,
     const int32_t* __restrict__ long_of,
     const int32_t* __restrict__ start_tab, int64_t n_rows, int64_t range_rows, int n_ranges,
-    const uint64_t* __restrict__ row_mask, int nq, const int32_t* __restrict__ uterm,
+    const uint64_t* __restrict__ row_mask, const QMask qm, int nq,
+    const int32_t* __restrict__ uterm,
     const int32_t* __restrict__ n_terms, const QTerm* __restrict__ ql,
     const int32_t* __restrict__ qu, const int32_t* __restrict__ qcount,
     const int32_t* __restrict__ qof, int2* __restrict__ cursors,
@@ -971,16 +992,23 @@ __global__ __launch_bounds__(kScanThreads) void sparse_scan_kernel(
       if (j < j1) batch(cur, j1 - j, i);  // cur = entries j .. j + 3
     }
   };
-  auto candidates = [&](int tile, uint64_t mw) {
+  // mask words per lane and tile: the shared 64-bit word, or per query the 32-bit half that holds
+  // the lane's four rows (four registers held across the step's compute, not eight)
+  constexpr int kMW = kQM ? kQW : 1;
+  constexpr int kMWBits = kQM ? 32 : 64;
+  using MaskWord = std::conditional_t<kQM, uint32_t, uint64_t>;
+  auto candidates = [&](int tile, const MaskWord (&mw)[kMW]) {
     const int32_t tlo = (int32_t)(lo + (int64_t)tile * kTile);
     const int32_t thi = tile_hi(tile);
     const int32_t r0 = tlo + 4 * lane;
-    const uint32_t mb = (uint32_t)(mw >> ((4 * lane) & 63)) & 0xfu;  // the lane's four rows
+    uint32_t mb[kMW];  // the lane's four rows
+#pragma unroll
+    for (int j = 0; j < kMW; ++j) mb[j] = (uint32_t)(mw[j] >> ((4 * lane) & (kMWBits - 1))) & 0xfu;
 #pragma unroll
     for (int i = 0; i < kQW; ++i) {
 #pragma unroll
       for (int h = 0; h < 4; ++h) {  // the lane's four rows, ascending
-        const bool cand = ((mb >> h) & 1u) && r0 + h < thi && hm[i][h] != 0u;
+        const bool cand = ((mb[kQM ? i : 0] >> h) & 1u) && r0 + h < thi && hm[i][h] != 0u;
         const float sc = h == 0 ? acc[i].x : h == 1 ? acc[i].y : h == 2 ? acc2[i].x : acc2[i].y;
         const int32_t r = r0 + h;
         if constexpr (kCollect) {
@@ -1011,6 +1039,10 @@ __global__ __launch_bounds__(kScanThreads) void sparse_scan_kernel(
   if (threadIdx.x < kTile / 4)
     reinterpret_cast<uint4*>(sbuf + (size_t)2 * kU * kTile)[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
   const int S = n_tiles * nSeg;
+  // the mask rows of the wave's four queries (null: unfiltered)
+  const uint64_t* mrow[kMW];
+#pragma unroll
+  for (int j = 0; j < kMW; ++j) mrow[j] = kQM ? qmask_row(row_mask, qm, qw[j]) : nullptr;
   unsigned long long tp[6] = {0, 0, 0, 0, 0, 0};
   unsigned long long t_a = 0, t_b = 0;
   (void)tp;
@@ -1034,11 +1066,21 @@ __global__ __launch_bounds__(kScanThreads) void sparse_scan_kernel(
     const int tile1 = last_seg ? tile + 1 : tile, seg1 = last_seg ? 0 : seg + 1;  // step s + 1
     // loaded now, used after this step's compute; lo is a multiple of 64, so the lane's four
     // rows tlo + 4 lane .. + 3 are bits of word tlo / 64 + lane / 16
-    uint64_t mw = ~0ull;
-    if (row_mask && last_seg) {
+    MaskWord mw[kMW];
+#pragma unroll
+    for (int j = 0; j < kMW; ++j) mw[j] = ~(MaskWord)0;
+    if constexpr (kQM) {
+      if (last_seg) {
+        const int64_t r0 = lo + (int64_t)tile * kTile + 4 * lane;  // a multiple of 4
+#pragma unroll
+        for (int i = 0; i < kQW; ++i)
+          if (mrow[i])  // uniform: a query belongs to the wave
+            mw[i] = r0 < hi ? reinterpret_cast<const uint32_t*>(mrow[i])[r0 >> 5] : 0u;
+      }
+    } else if (row_mask && last_seg) {
       const int64_t tlo = lo + (int64_t)tile * kTile;
       const int64_t w0 = tlo + 64 * (lane >> 4);
-      mw = w0 < hi ? row_mask[w0 >> 6] : 0ull;
+      mw[0] = w0 < hi ? row_mask[w0 >> 6] : 0ull;
     }
     ARMI_PROF_T(t_a);
     if (s + 1 < S) issue(tile1, seg1);
@@ -1141,6 +1183,48 @@ __global__ __launch_bounds__(kScanThreads) void sparse_scan_kernel(
     pr[11] = t_exit;
   }
 #endif
+}
+
+template <bool kCollect>
+__global__ __launch_bounds__(kScanThreads) void sparse_scan_kernel(
+    const int32_t* __restrict__ term_ptr, const int2* __restrict__ post,
+    const int32_t* __restrict__ long_of,
+    const int32_t* __restrict__ start_tab, int64_t n_rows, int64_t range_rows, int n_ranges,
+    const uint64_t* __restrict__ row_mask, int nq, const int32_t* __restrict__ uterm,
+    const int32_t* __restrict__ n_terms, const QTerm* __restrict__ ql,
+    const int32_t* __restrict__ qu, const int32_t* __restrict__ qcount,
+    const int32_t* __restrict__ qof, int2* __restrict__ cursors,
+    float* __restrict__ cand_key, int32_t* __restrict__ cand_row, float* __restrict__ cand_bound,
+    const float* __restrict__ thr, int* __restrict__ coll_count, float* __restrict__ coll_key,
+    int32_t* __restrict__ coll_row, int dbg, const int32_t* __restrict__ dense_of,
+    const uint32_t* __restrict__ dense_val, int64_t dense_stride,
+    const uint32_t* __restrict__ done_flags) {
+  sparse_scan_body<kCollect, false>(term_ptr, post, long_of, start_tab, n_rows, range_rows, n_ranges,
+                                    row_mask, QMask{}, nq, uterm, n_terms, ql, qu, qcount, qof,
+                                    cursors, cand_key, cand_row, cand_bound, thr, coll_count, coll_key,
+                                    coll_row, dbg, dense_of, dense_val, dense_stride, done_flags);
+}
+
+// the per-query-mask sibling (armi_sparse_topk_qmask)
+template <bool kCollect>
+__global__ __launch_bounds__(kScanThreads) void sparse_scan_qmask_kernel(
+    const int32_t* __restrict__ term_ptr, const int2* __restrict__ post,
+    const int32_t* __restrict__ long_of,
+    const int32_t* __restrict__ start_tab, int64_t n_rows, int64_t range_rows, int n_ranges,
+    const uint64_t* __restrict__ row_masks, const QMask qm, int nq,
+    const int32_t* __restrict__ uterm,
+    const int32_t* __restrict__ n_terms, const QTerm* __restrict__ ql,
+    const int32_t* __restrict__ qu, const int32_t* __restrict__ qcount,
+    const int32_t* __restrict__ qof, int2* __restrict__ cursors,
+    float* __restrict__ cand_key, int32_t* __restrict__ cand_row, float* __restrict__ cand_bound,
+    const float* __restrict__ thr, int* __restrict__ coll_count, float* __restrict__ coll_key,
+    int32_t* __restrict__ coll_row, int dbg, const int32_t* __restrict__ dense_of,
+    const uint32_t* __restrict__ dense_val, int64_t dense_stride,
+    const uint32_t* __restrict__ done_flags) {
+  sparse_scan_body<kCollect, true>(term_ptr, post, long_of, start_tab, n_rows, range_rows, n_ranges,
+                                   row_masks, qm, nq, uterm, n_terms, ql, qu, qcount, qof, cursors,
+                                   cand_key, cand_row, cand_bound, thr, coll_count, coll_key,
+                                   coll_row, dbg, dense_of, dense_val, dense_stride, done_flags);
 }
 
 // Order-preserving map of a float to uint32 (larger float -> larger key; -inf lowest).
@@ -1318,10 +1402,14 @@ static_assert(kHelpSort >= kCollectCap, "the collect list sorts in the same buff
 constexpr size_t kCollectLds =
     (size_t)kHelpSort * 8 + kHelpRows * 4 + kHelpRows + (size_t)kMaxTerms * 16 + 64;
 
-__global__ __launch_bounds__(256) void sparse_collect_merge_kernel(
+// kQM = true (sparse_collect_merge_qmask_kernel): the helpers test a row against the query's own
+// row of the mask stack, and every query's flags leave with ARMI_FLAG_QMASK set (this is the
+// pass's last kernel, and the only writer of a query's flags at that point).
+template <bool kQM>
+__device__ __forceinline__ void sparse_collect_merge_body(
     const int* __restrict__ coll_count, float* __restrict__ coll_key,
     int32_t* __restrict__ coll_row, int* __restrict__ help_done, int nq, int q_first, int k,
-    int64_t ordinal_base, int64_t n_rows, const uint64_t* __restrict__ row_mask,
+    int64_t ordinal_base, int64_t n_rows, const uint64_t* __restrict__ row_mask, const QMask qm,
     const int32_t* __restrict__ term_ptr, const int2* __restrict__ post,
     const int32_t* __restrict__ dense_of, const uint32_t* __restrict__ dense_val,
     int64_t dense_stride, const int32_t* __restrict__ uterm, const QTerm* __restrict__ qlist,
@@ -1349,11 +1437,20 @@ __global__ __launch_bounds__(256) void sparse_collect_merge_kernel(
     }
     if (lane == 0) {
       out_count[qg] = nv;
-      flags[ql] |= ARMI_FLAG_FALLBACK;
+      flags[ql] |= kQM ? (ARMI_FLAG_FALLBACK | ARMI_FLAG_QMASK) : ARMI_FLAG_FALLBACK;
     }
   };
   if ((int)blockIdx.x < nq) {  // the query's own workgroup
     const int ql = blockIdx.x;
+    if constexpr (kQM) {
+      // a certified query's flags are final and nobody else writes them; the others get the bit
+      // from whoever answers them (write_out)
+      const uint32_t f = flags[ql];
+      if (f & ARMI_FLAG_CERTIFIED) {  // workgroup-uniform
+        if (tid == 0) flags[ql] = f | ARMI_FLAG_QMASK;
+        return;
+      }
+    }
     if (flags[ql] & ARMI_FLAG_CERTIFIED) return;  // workgroup-uniform
     const int total = coll_count[ql];
     if (total > kCollectCap) return;  // overflowed: the helpers answer it
@@ -1392,6 +1489,8 @@ __global__ __launch_bounds__(256) void sparse_collect_merge_kernel(
     __syncthreads();
     const int slot = sh[0];
     const int nt = qcount[slot];
+    // kQM: the query's own mask row (uniform; null: unfiltered)
+    const uint64_t* __restrict__ qrow = kQM ? qmask_row(row_mask, qm, ql) : nullptr;
     for (int j = tid; j < nt; j += 256) {  // the query's terms, ascending
       const int32_t t = uterm[qu[slot * kQStride + j]];
       tw[j] = qlist[slot * kQStride + j].w;
@@ -1476,7 +1575,8 @@ __global__ __launch_bounds__(256) void sparse_collect_merge_kernel(
         const int e = tid + 256 * i;
         const int32_t r = r0 + e;
         const bool on = r < chi && has[e] &&
-                        (!row_mask || ((row_mask[r >> 6] >> (r & 63)) & 1ull));
+                        (kQM ? (!qrow || ((qrow[r >> 6] >> (r & 63)) & 1ull))
+                             : (!row_mask || ((row_mask[r >> 6] >> (r & 63)) & 1ull)));
         if (on && armi::approx_better(acc[e], r, kk, kr)) {
           const int s2 = atomicAdd(&sh[1], 1);
           skey[kBestPad + s2] = acc[e];
@@ -1522,6 +1622,38 @@ __global__ __launch_bounds__(256) void sparse_collect_merge_kernel(
       write_out(ql);
     }
   }
+}
+
+__global__ __launch_bounds__(256) void sparse_collect_merge_kernel(
+    const int* __restrict__ coll_count, float* __restrict__ coll_key,
+    int32_t* __restrict__ coll_row, int* __restrict__ help_done, int nq, int q_first, int k,
+    int64_t ordinal_base, int64_t n_rows, const uint64_t* __restrict__ row_mask,
+    const int32_t* __restrict__ term_ptr, const int2* __restrict__ post,
+    const int32_t* __restrict__ dense_of, const uint32_t* __restrict__ dense_val,
+    int64_t dense_stride, const int32_t* __restrict__ uterm, const QTerm* __restrict__ qlist,
+    const int32_t* __restrict__ qu, const int32_t* __restrict__ qcount,
+    const int32_t* __restrict__ qof, float* __restrict__ out_scores,
+    int64_t* __restrict__ out_ids, int32_t* __restrict__ out_count, uint32_t* __restrict__ flags) {
+  sparse_collect_merge_body<false>(coll_count, coll_key, coll_row, help_done, nq, q_first, k,
+                                   ordinal_base, n_rows, row_mask, QMask{}, term_ptr, post, dense_of,
+                                   dense_val, dense_stride, uterm, qlist, qu, qcount, qof,
+                                   out_scores, out_ids, out_count, flags);
+}
+
+__global__ __launch_bounds__(256) void sparse_collect_merge_qmask_kernel(
+    const int* __restrict__ coll_count, float* __restrict__ coll_key,
+    int32_t* __restrict__ coll_row, int* __restrict__ help_done, int nq, int q_first, int k,
+    int64_t ordinal_base, int64_t n_rows, const uint64_t* __restrict__ row_masks, const QMask qm,
+    const int32_t* __restrict__ term_ptr, const int2* __restrict__ post,
+    const int32_t* __restrict__ dense_of, const uint32_t* __restrict__ dense_val,
+    int64_t dense_stride, const int32_t* __restrict__ uterm, const QTerm* __restrict__ qlist,
+    const int32_t* __restrict__ qu, const int32_t* __restrict__ qcount,
+    const int32_t* __restrict__ qof, float* __restrict__ out_scores,
+    int64_t* __restrict__ out_ids, int32_t* __restrict__ out_count, uint32_t* __restrict__ flags) {
+  sparse_collect_merge_body<true>(coll_count, coll_key, coll_row, help_done, nq, q_first, k,
+                                   ordinal_base, n_rows, row_masks, qm, term_ptr, post, dense_of,
+                                   dense_val, dense_stride, uterm, qlist, qu, qcount, qof,
+                                   out_scores, out_ids, out_count, flags);
 }
 
 #include "sparse_filter.h"
@@ -2420,19 +2552,20 @@ size_t armi_sparse_workspace_bytes(const armi_sparse_index* idx, int n_queries, 
   return carve(nullptr, idx).bytes;
 }
 
-int armi_sparse_topk(const armi_sparse_index* idx, const int32_t* q_indptr,
-                     const int32_t* q_indices, const float* q_values, int n_queries, int k,
-                     const uint64_t* row_mask, float* out_scores, int64_t* out_ids,
-                     int32_t* out_count, uint32_t* out_flags, void* workspace,
-                     size_t workspace_bytes, hipStream_t stream) {
-  ARMI_REQUIRE(idx != nullptr, "armi_sparse_topk: index is null");
-  ARMI_REQUIRE(k >= 1 && k <= kMaxK, "armi_sparse_topk: k must be in [1, 240]");
-  if (n_queries <= 0) return ARMI_OK;
-  ARMI_REQUIRE(q_indptr && q_indices && q_values && out_scores && out_ids && out_count &&
-                   out_flags && workspace,
-               "armi_sparse_topk: null pointer argument");
-  ARMI_REQUIRE(workspace_bytes >= armi_sparse_workspace_bytes(idx, n_queries, k),
-               "armi_sparse_topk: workspace too small");
+}  // extern "C"
+
+namespace {
+
+// The launch sequence of armi_sparse_topk and armi_sparse_topk_qmask (arguments checked by the
+// entry points). q_mask == nullptr: row_mask is the call's one shared mask (or null). q_mask set:
+// row_mask is the [n_masks][mask_stride] stack and every kernel that tests a mask runs its
+// per-query sibling; the pass offset q0 reaches the kernels as q_mask + q0.
+int sparse_topk_launch(const armi_sparse_index* idx, const int32_t* q_indptr,
+                       const int32_t* q_indices, const float* q_values, int n_queries, int k,
+                       const uint64_t* row_mask, int64_t mask_stride, const int32_t* q_mask,
+                       int n_masks, float* out_scores, int64_t* out_ids, int32_t* out_count,
+                       uint32_t* out_flags, void* workspace, hipStream_t stream) {
+  const bool qmask = q_mask != nullptr;
   ARMI_HIP(hipSetDevice(idx->device));
   const Workspace w = carve(workspace, idx);
 #ifdef ARMI_SPARSE_PROFILE
@@ -2448,6 +2581,12 @@ int armi_sparse_topk(const armi_sparse_index* idx, const int32_t* q_indptr,
   if (int rc = armi::allow_lds(sparse_scan_kernel<false>, kScanLds)) return rc;
   if (int rc = armi::allow_lds(sparse_scan_kernel<true>, kScanLds)) return rc;
   if (int rc = armi::allow_lds(sparse_filter_scan_kernel, kFLds)) return rc;
+  if (qmask) {
+    if (int rc = armi::allow_lds(sparse_collect_merge_qmask_kernel, kCollectLds)) return rc;
+    if (int rc = armi::allow_lds(sparse_scan_qmask_kernel<false>, kScanLds)) return rc;
+    if (int rc = armi::allow_lds(sparse_scan_qmask_kernel<true>, kScanLds)) return rc;
+    if (int rc = armi::allow_lds(sparse_filter_scan_qmask_kernel, kFLds)) return rc;
+  }
   const int n_help = std::max(1, std::min(kMaxHelp, kCollectCap / k));
   // the MFMA filter answers what it can certify; kc = the rescored candidates per query
   const bool filter = idx->filter_ok && idx->filter_on && k <= kFMaxK && idx->n_ranges > 0;
@@ -2461,9 +2600,11 @@ int armi_sparse_topk(const armi_sparse_index* idx, const int32_t* q_indptr,
   for (int q0 = 0; q0 < n_queries; q0 += kQB) {
     const int nqp = std::min(kQB, n_queries - q0);
     uint32_t* pflags = out_flags + q0;
+    const QMask qm{qmask ? q_mask + q0 : nullptr, mask_stride, n_masks, nqp};
     if (idx->n_rows == 0) {
       ARMI_HIP(hipMemsetAsync(out_count + q0, 0, sizeof(int32_t) * nqp, stream));
-      ARMI_HIP(hipMemsetAsync(pflags, 0, sizeof(uint32_t) * nqp, stream));
+      ARMI_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(pflags),
+                                 qmask ? (int)ARMI_FLAG_QMASK : 0, nqp, stream));
       ARMI_HIP(hipMemsetAsync(out_ids + (size_t)q0 * k, 0xff, sizeof(int64_t) * nqp * k, stream));
       continue;
     }
@@ -2480,7 +2621,17 @@ int armi_sparse_topk(const armi_sparse_index* idx, const int32_t* q_indptr,
           w.qcount, w.qof, pflags, w.coll_count, fp);
     ARMI_LAUNCHED("pass_terms_kernel");
     if (filter) {
-      const int rc_f = armi::timed_kernel(
+      const int rc_f =
+          qmask ? armi::timed_kernel(
+                      scan_slot, sparse_filter_scan_qmask_kernel, dim3(idx->n_ranges),
+                      dim3(kFThreads), kFLds, stream, (const int32_t*)idx->term_ptr,
+                      reinterpret_cast<const int2*>(idx->post), (const int32_t*)idx->long_of,
+                      (const int32_t*)idx->start_tab, idx->n_rows, idx->range_rows, idx->n_ranges,
+                      row_mask, qm, (const int32_t*)w.uterm, (const int32_t*)w.n_terms,
+                      (const int32_t*)idx->col8_of, (const uint8_t*)idx->dense_u8,
+                      idx->dense8_stride, (const float*)idx->term_scale, (const uint16_t*)w.fB,
+                      (const float*)w.fscale, w.cand_key, w.cand_row, w.cand_bound)
+                : armi::timed_kernel(
           scan_slot, sparse_filter_scan_kernel, dim3(idx->n_ranges), dim3(kFThreads),
           kFLds, stream, (const int32_t*)idx->term_ptr, reinterpret_cast<const int2*>(idx->post),
           (const int32_t*)idx->long_of, (const int32_t*)idx->start_tab, idx->n_rows,
@@ -2550,6 +2701,14 @@ int armi_sparse_topk(const armi_sparse_index* idx, const int32_t* q_indptr,
     // (the kernel exits at once when it answered all of them)
     armi::TimedLaunch tl;
     if (!filter && tl.begin(scan_slot, stream) < 0) return ARMI_ERR_HIP;
+    if (qmask)
+      sparse_scan_qmask_kernel<false><<<dim3(idx->n_ranges), dim3(kScanThreads), kScanLds, stream>>>(
+          idx->term_ptr, reinterpret_cast<const int2*>(idx->post), idx->long_of, idx->start_tab,
+          idx->n_rows, idx->range_rows, idx->n_ranges, row_mask, qm, nqp, w.uterm, w.n_terms, w.ql,
+          w.qu, w.qcount, w.qof, w.cursors, w.cand_key, w.cand_row, w.cand_bound, nullptr, nullptr,
+          nullptr, nullptr, dbg, idx->dense_of, idx->dense_val, idx->dense_stride,
+          filter ? pflags : nullptr);
+    else
     sparse_scan_kernel<false><<<dim3(idx->n_ranges), dim3(kScanThreads), kScanLds, stream>>>(
         idx->term_ptr, reinterpret_cast<const int2*>(idx->post), idx->long_of, idx->start_tab, idx->n_rows,
         idx->range_rows, idx->n_ranges, row_mask, nqp, w.uterm, w.n_terms, w.ql, w.qu, w.qcount, w.qof,
@@ -2592,12 +2751,26 @@ int armi_sparse_topk(const armi_sparse_index* idx, const int32_t* q_indptr,
         w.cand_key, w.cand_row, w.cand_bound, idx->n_ranges, q0, k, idx->ordinal_base,
         out_scores, out_ids, out_count, pflags, w.kth);
     ARMI_LAUNCHED("sparse_merge_kernel");
+    if (qmask)
+      sparse_scan_qmask_kernel<true><<<dim3(idx->n_ranges), dim3(kScanThreads), kScanLds, stream>>>(
+          idx->term_ptr, reinterpret_cast<const int2*>(idx->post), idx->long_of, idx->start_tab,
+          idx->n_rows, idx->range_rows, idx->n_ranges, row_mask, qm, nqp, w.uterm, w.n_terms, w.ql,
+          w.qu, w.qcount, w.qof, w.cursors, nullptr, nullptr, nullptr, w.kth, w.coll_count,
+          w.coll_key, w.coll_row, dbg, idx->dense_of, idx->dense_val, idx->dense_stride, nullptr);
+    else
     sparse_scan_kernel<true><<<dim3(idx->n_ranges), dim3(kScanThreads), kScanLds, stream>>>(
         idx->term_ptr, reinterpret_cast<const int2*>(idx->post), idx->long_of, idx->start_tab, idx->n_rows,
         idx->range_rows, idx->n_ranges, row_mask, nqp, w.uterm, w.n_terms, w.ql, w.qu, w.qcount, w.qof,
         w.cursors, nullptr, nullptr, nullptr, w.kth, w.coll_count, w.coll_key, w.coll_row, dbg,
         idx->dense_of, idx->dense_val, idx->dense_stride, nullptr);
     ARMI_LAUNCHED("sparse_collect_kernel");
+    if (qmask)
+      sparse_collect_merge_qmask_kernel<<<dim3(nqp + n_help), dim3(256), kCollectLds, stream>>>(
+          w.coll_count, w.coll_key, w.coll_row, w.coll_count + kQB, nqp, q0, k, idx->ordinal_base,
+          idx->n_rows, row_mask, qm, idx->term_ptr, reinterpret_cast<const int2*>(idx->post),
+          idx->dense_of, idx->dense_val, idx->dense_stride, w.uterm, w.ql, w.qu, w.qcount, w.qof,
+          out_scores, out_ids, out_count, pflags);
+    else
     sparse_collect_merge_kernel<<<dim3(nqp + n_help), dim3(256), kCollectLds, stream>>>(
         w.coll_count, w.coll_key, w.coll_row, w.coll_count + kQB, nqp, q0,
         k, idx->ordinal_base, idx->n_rows, row_mask, idx->term_ptr,
@@ -2608,6 +2781,51 @@ int armi_sparse_topk(const armi_sparse_index* idx, const int32_t* q_indptr,
   }
   if (int rc = stage.end()) return rc;
   return ARMI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int armi_sparse_topk(const armi_sparse_index* idx, const int32_t* q_indptr,
+                     const int32_t* q_indices, const float* q_values, int n_queries, int k,
+                     const uint64_t* row_mask, float* out_scores, int64_t* out_ids,
+                     int32_t* out_count, uint32_t* out_flags, void* workspace,
+                     size_t workspace_bytes, hipStream_t stream) {
+  ARMI_REQUIRE(idx != nullptr, "armi_sparse_topk: index is null");
+  ARMI_REQUIRE(k >= 1 && k <= kMaxK, "armi_sparse_topk: k must be in [1, 240]");
+  if (n_queries <= 0) return ARMI_OK;
+  ARMI_REQUIRE(q_indptr && q_indices && q_values && out_scores && out_ids && out_count &&
+                   out_flags && workspace,
+               "armi_sparse_topk: null pointer argument");
+  ARMI_REQUIRE(workspace_bytes >= armi_sparse_workspace_bytes(idx, n_queries, k),
+               "armi_sparse_topk: workspace too small");
+  return sparse_topk_launch(idx, q_indptr, q_indices, q_values, n_queries, k, row_mask, 0, nullptr,
+                            0, out_scores, out_ids, out_count, out_flags, workspace, stream);
+}
+
+int armi_sparse_topk_qmask(const armi_sparse_index* idx, const int32_t* q_indptr,
+                           const int32_t* q_indices, const float* q_values, int n_queries, int k,
+                           const uint64_t* row_masks, int64_t mask_stride_words,
+                           const int32_t* q_mask, int n_masks, float* out_scores,
+                           int64_t* out_ids, int32_t* out_count, uint32_t* out_flags,
+                           void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  // (what needs no index first, so that those answers do not depend on the others)
+  ARMI_REQUIRE(n_masks >= 0, "armi_sparse_topk_qmask: n_masks < 0");
+  ARMI_REQUIRE(mask_stride_words >= 0, "armi_sparse_topk_qmask: mask_stride_words < 0");
+  ARMI_REQUIRE(idx != nullptr, "armi_sparse_topk_qmask: index is null");
+  ARMI_REQUIRE(k >= 1 && k <= kMaxK, "armi_sparse_topk_qmask: k must be in [1, 240]");
+  ARMI_REQUIRE(mask_stride_words >= (idx->n_rows + 63) / 64,
+               "armi_sparse_topk_qmask: mask_stride_words < ceil(rows / 64)");
+  if (n_queries <= 0) return ARMI_OK;
+  ARMI_REQUIRE(q_indptr && q_indices && q_values && q_mask && (row_masks || n_masks == 0) &&
+                   out_scores && out_ids && out_count && out_flags && workspace,
+               "armi_sparse_topk_qmask: null pointer argument");
+  ARMI_REQUIRE(workspace_bytes >= armi_sparse_workspace_bytes(idx, n_queries, k),
+               "armi_sparse_topk_qmask: workspace too small");
+  return sparse_topk_launch(idx, q_indptr, q_indices, q_values, n_queries, k, row_masks,
+                            mask_stride_words, q_mask, n_masks, out_scores, out_ids, out_count,
+                            out_flags, workspace, stream);
 }
 
 int armi_sparse_index_set_filter(armi_sparse_index* index, int enable, int* usable) {

@@ -438,10 +438,23 @@ __device__ __forceinline__ void filter_prep_block(int nU, const QTerm* __restric
 // its held terms' cursors sit in lane 2 seg + j of creg (x: posting cursor, or -(d + 1) for
 // dense column d, or kFNone; y: row of the cursor's posting) and their scales in sreg. The
 // MFMAs: wave w owns row blocks 4 w .. 4 w + 3 (32 rows each) x both 32-query halves.
-__global__ __launch_bounds__(kFThreads) void sparse_filter_scan_kernel(
+//
+// kQM = true (sparse_filter_scan_qmask_kernel): row_mask is the caller's [n_masks][stride] stack
+// and each query column is filtered by its own row of it (qm, see QMask). In the epilogue a lane
+// holds, per row block i and query half h, the scores of one query column: it needs that
+// column's 32 mask bits per (i, h). They are loaded inside the epilogue: the kernel runs at 246 of
+// its 256 registers, and words issued ahead of the step's issue() would have to be held across
+// the step's MFMAs (that form spilled). So a tile's last step waits for the ring loads in flight
+// once. A pass without a filtered query (uniform) loads nothing. The `full` shortcut is not kept
+// in this instance: every form tried that had both the shortcut and the per-query path in the
+// step loop spilled (100 to 350 B of scratch per lane); instead every tile runs one path in which
+// a score is ANDed with its row's sign-extended bit (two VALU per score, no select), which for an
+// unfiltered pass is the range test alone. DESIGN.md section 15 has the measured cost.
+template <bool kQM>
+__device__ __forceinline__ void sparse_filter_scan_body(
     const int32_t* __restrict__ term_ptr, const int2* __restrict__ post,
     const int32_t* __restrict__ long_of, const int32_t* __restrict__ start_tab, int64_t n_rows,
-    int64_t range_rows, int n_ranges, const uint64_t* __restrict__ row_mask,
+    int64_t range_rows, int n_ranges, const uint64_t* __restrict__ row_mask, const QMask qm,
     const int32_t* __restrict__ uterm, const int32_t* __restrict__ n_terms,
     const int32_t* __restrict__ col8_of, const uint8_t* __restrict__ dense_u8, int64_t stride8,
     const float* __restrict__ term_scale, const uint16_t* __restrict__ fB,
@@ -485,6 +498,14 @@ __global__ __launch_bounds__(kFThreads) void sparse_filter_scan_kernel(
   const int rev2 = 2 * (63 - lane);
   fp4 ring[kFDepth][2];
   auto tile_hi = [&](int tile) { return (int32_t)min(lo + (int64_t)(tile + 1) * kFT, hi); };
+  // per-query masks: the mask of the lane's query column in each half (-1: unfiltered), and
+  // whether the pass has a filtered query at all
+  auto mask_of = [&](int q) {
+    const int32_t m = q < qm.nq ? qm.q_mask[q] : -1;
+    return m >= 0 && m < qm.n_masks ? m : -1;
+  };
+  bool any_mask = false;  // workgroup-uniform: every wave looks at all 64 queries
+  if constexpr (kQM) any_mask = __ballot(mask_of(lane) >= 0) != 0ull;
   // step s's loads into ring slot `slot`: every lane issues the same two loads per step (steps
   // past the end and absent terms read a fixed in-bounds address), so the waits the compiler
   // counts stay exact
@@ -649,7 +670,7 @@ __global__ __launch_bounds__(kFThreads) void sparse_filter_scan_kernel(
   auto epilogue = [&](int tile) {
     const int32_t tlo = (int32_t)(lo + (int64_t)tile * kFT);
     const int32_t thi = tile_hi(tile);
-    const bool full = thi - tlo == kFT && !row_mask;  // uniform
+    const bool full = !kQM && thi - tlo == kFT && !row_mask;  // uniform
     // (as their bit patterns: every key is >= +0, so the unsigned order is the float order, and
     // integer max / med3 need no canonicalising copies of bit-built floats)
     uint32_t top[2][4];
@@ -673,6 +694,33 @@ __global__ __launch_bounds__(kFThreads) void sparse_filter_scan_kernel(
           net(0, acc[i][0][v], 16 * i + v);
           net(1, acc[i][1][v], 16 * i + v);
         }
+    } else if constexpr (kQM) {
+      // One query half at a time, its mask index read again per tile (not held across the
+      // steps) and its four words loaded together.
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        __builtin_amdgcn_sched_barrier(0);
+        const int32_t mq = any_mask ? mask_of(32 * h + (lane & 31)) : -1;
+        const uint32_t* mrow32 =
+            reinterpret_cast<const uint32_t*>(row_mask + (size_t)max(mq, 0) * qm.stride);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int32_t rb = tlo + 32 * (4 * wave + i);  // a multiple of 32
+          // the block's rows inside the range, then the query's own bits of them (the 32-bit
+          // half rb / 32 of its mask row), shifted to the lane's rows
+          const int32_t left = thi - rb;  // uniform
+          uint32_t mb = left >= 32 ? 0xffffffffu : (left > 0 ? (1u << left) - 1u : 0u);
+          if (mq >= 0 && left > 0) mb &= mrow32[rb >> 5];
+          mb >>= 4 * (lane >> 5);
+          // a cleared bit zeroes the score (every score is >= +0) by an AND with the sign-extended
+          // bit, not by a select: the selects' lane masks did not fit the scalar registers
+#pragma unroll
+          for (int v = 0; v < 16; ++v) {
+            const int32_t keep = (int32_t)(mb << (31 - (8 * (v >> 2) + (v & 3)))) >> 31;
+            net(h, __uint_as_float(__float_as_uint(acc[i][h][v]) & (uint32_t)keep), 16 * i + v);
+          }
+        }
+      }
     } else {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -798,6 +846,34 @@ __global__ __launch_bounds__(kFThreads) void sparse_filter_scan_kernel(
     }
     if (lane == 0) cand_bound[base] = bq[n];
   }
+}
+
+__global__ __launch_bounds__(kFThreads) void sparse_filter_scan_kernel(
+    const int32_t* __restrict__ term_ptr, const int2* __restrict__ post,
+    const int32_t* __restrict__ long_of, const int32_t* __restrict__ start_tab, int64_t n_rows,
+    int64_t range_rows, int n_ranges, const uint64_t* __restrict__ row_mask,
+    const int32_t* __restrict__ uterm, const int32_t* __restrict__ n_terms,
+    const int32_t* __restrict__ col8_of, const uint8_t* __restrict__ dense_u8, int64_t stride8,
+    const float* __restrict__ term_scale, const uint16_t* __restrict__ fB,
+    const float* __restrict__ fscale, float* __restrict__ cand_key,
+    int32_t* __restrict__ cand_row, float* __restrict__ cand_bound) {
+  sparse_filter_scan_body<false>(term_ptr, post, long_of, start_tab, n_rows, range_rows, n_ranges,
+                                 row_mask, QMask{}, uterm, n_terms, col8_of, dense_u8, stride8,
+                                 term_scale, fB, fscale, cand_key, cand_row, cand_bound);
+}
+
+__global__ __launch_bounds__(kFThreads) void sparse_filter_scan_qmask_kernel(
+    const int32_t* __restrict__ term_ptr, const int2* __restrict__ post,
+    const int32_t* __restrict__ long_of, const int32_t* __restrict__ start_tab, int64_t n_rows,
+    int64_t range_rows, int n_ranges, const uint64_t* __restrict__ row_masks, const QMask qm,
+    const int32_t* __restrict__ uterm, const int32_t* __restrict__ n_terms,
+    const int32_t* __restrict__ col8_of, const uint8_t* __restrict__ dense_u8, int64_t stride8,
+    const float* __restrict__ term_scale, const uint16_t* __restrict__ fB,
+    const float* __restrict__ fscale, float* __restrict__ cand_key,
+    int32_t* __restrict__ cand_row, float* __restrict__ cand_bound) {
+  sparse_filter_scan_body<true>(term_ptr, post, long_of, start_tab, n_rows, range_rows, n_ranges,
+                                 row_masks, qm, uterm, n_terms, col8_of, dense_u8, stride8,
+                                 term_scale, fB, fscale, cand_key, cand_row, cand_bound);
 }
 
 // Per query of the pass, in up to two rounds. Round 1: the kc best keys of the pool (the entries

@@ -180,7 +180,8 @@ class QueryBatcher:
 
     def _mixed_filters(self) -> bool:
         r = self.retriever
-        return (r.config.filter_list_rows > 0 or r.config.filter_query_masks) and r._world == 1
+        return (r.config.filter_list_rows > 0 or r.config.filter_query_masks or
+                r.config.filter_query_masks_sparse) and r._world == 1
 
     def _serve(self, reqs: list[_Request]) -> None:
         try:

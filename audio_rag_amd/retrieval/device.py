@@ -122,7 +122,7 @@ def _check_row_lists(list_ptr: torch.Tensor, list_rows: torch.Tensor, q_list: to
 
 def _check_row_masks(row_masks: torch.Tensor, q_mask: torch.Tensor, n_queries: int,
                      n_rows: int) -> tuple[int, int]:
-    """Argument checks of DenseIndex.topk_masks (include/armi.h, armi_dense_topk_qmask); returns
+    """Argument checks of DenseIndex.topk_masks and SparseIndex.topk_masks (include/armi.h); returns
     (n_masks, stride in words). q_mask is checked for its range only when it lives on the host (a
     device q_mask is not read back: that would synchronise every call; the kernels treat an entry
     outside [-1, n_masks) as -1)."""
@@ -444,6 +444,30 @@ class SparseIndex:
         call("armi_sparse_topk", self._handle, ptr(q_indptr), ptr(q_indices), ptr(q_values), b, k,
              ptr(row_mask), ptr(out.scores), ptr(out.ids), ptr(out.count), ptr(out.flags),
              ptr(workspace), workspace.numel(), stream_handle())
+        return out
+
+    def topk_masks(self, q_indptr: torch.Tensor, q_indices: torch.Tensor, q_values: torch.Tensor,
+                   k: int, row_masks: torch.Tensor, q_mask: torch.Tensor,
+                   workspace: torch.Tensor | None = None) -> TopK:
+        """Sparse dot top-k of every query under its own row mask, in the launches of one topk
+        call (armi_sparse_topk_qmask): row_masks int64 [n_masks, words] device bitmasks (topk's
+        row_mask convention, one per row of the tensor; [0, words] when no query is filtered),
+        q_mask int32 [B] the mask of each query or -1 for none (a host tensor is uploaded). The
+        same ids, scores and counts as topk(row_mask=...) called once per mask; flags carry
+        ARMI_FLAG_QMASK. Any batch size and k that topk takes; the workspace is topk's."""
+        _check_k(k)
+        b = int(q_indptr.numel()) - 1
+        dev = self.device
+        n_masks, stride = _check_row_masks(row_masks, q_mask, b, self.n_rows)
+        q_mask = _on_device(q_mask, dev)
+        out = TopK.empty(b, k, dev, rank=False)
+        if b == 0:
+            return out
+        workspace = _workspace(workspace, self.workspace_bytes(b, k), dev)
+        call("armi_sparse_topk_qmask", self._handle, ptr(q_indptr), ptr(q_indices), ptr(q_values),
+             b, k, ptr(row_masks) if n_masks else None, stride, ptr(q_mask), n_masks,
+             ptr(out.scores), ptr(out.ids), ptr(out.count), ptr(out.flags), ptr(workspace),
+             workspace.numel(), stream_handle())
         return out
 
     @staticmethod

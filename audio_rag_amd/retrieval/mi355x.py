@@ -88,17 +88,18 @@ class FilterGroup:
     queries: list
     matches: int = -1       # rows the filter matches (-1: not counted, the knob is off / no filter)
     rowlist: bool = False   # ranked from the matching rows (armi_*_rowlist_topk), else a masked scan
-    qmask: bool = False     # its masked dense scan is shared with the other qmask groups of the
-    #                         call (armi_dense_topk_qmask), else a masked search of its own
+    qmask: bool = False     # its masked scan is shared with the other qmask groups of the call
+    #                         (armi_dense_topk_qmask; sparse mode: armi_sparse_topk_qmask), else a
+    #                         masked search of its own
 
 
 QMASK_MODES = ("dense", "legacy_dense", "hybrid")
-QMASK_MAX_QUERIES = 128  # queries of one armi_dense_topk_qmask call
+QMASK_MAX_QUERIES = 128  # queries of one armi_dense_topk_qmask call (sparse mode cuts alike)
 
 
 def plan_filter_groups(filters: list, n_rows: int, knob: int, count_matches,
                        query_masks: bool = False, mode: str = "dense", tail_rows: int = 0,
-                       qmask_supported=None) -> list[FilterGroup]:
+                       qmask_supported=None, sparse_masks: bool = False) -> list[FilterGroup]:
     """Groups the queries of a batch by filter (in order of first appearance) and picks each
     group's path. A group of q queries whose filter matches m of the collection's n_rows rows is
     ranked from its row list iff the knob is on (filter_list_rows > 0), m <= knob and
@@ -113,9 +114,14 @@ def plan_filter_groups(filters: list, n_rows: int, knob: int, count_matches,
     their dense scans become one scan of the int8 image per 64 queries in which every query
     carries its own mask (DenseIndex.topk_masks). All of: query_masks (the filter_query_masks knob)
     on, at least two such groups (one group is one masked search already), mode dense /
-    legacy_dense / hybrid (the sparse kernels have no such form), no tail rows (nor has the live
-    tail pass) and qmask_supported(queries of a call) -> bool (the dense index's answer for the
-    leg's k: an int8 image, k <= 64). Otherwise they stay one masked search per group."""
+    legacy_dense / hybrid, no tail rows (the live tail pass has no such form) and
+    qmask_supported(queries of a call) -> bool (the dense index's answer for the leg's k: an int8
+    image, k <= 64). Otherwise they stay one masked search per group.
+
+    Mode sparse has its own rule: sparse_masks (the filter_query_masks_sparse knob) on, at least
+    two such groups and no tail rows (armi_sparse_tail_topk takes one mask). The sparse form
+    (SparseIndex.topk_masks) has no shape limit, so neither query_masks nor qmask_supported is
+    consulted."""
     groups: dict = {}
     for i, f in enumerate(filters):
         g = groups.get(filter_key(f))
@@ -133,6 +139,9 @@ def plan_filter_groups(filters: list, n_rows: int, knob: int, count_matches,
         if qmask_supported(min(n, QMASK_MAX_QUERIES)):
             for g in rest:
                 g.qmask = True
+    if mode == "sparse" and sparse_masks and len(rest) >= 2 and tail_rows == 0:
+        for g in rest:
+            g.qmask = True
     return list(groups.values())
 
 
@@ -419,7 +428,8 @@ class MI355XRetriever(BaseRetriever):
         takes one filter per request, api/v1/query.py:41). With config.filter_list_rows > 0 the
         queries are grouped by filter and selective groups are ranked from their matching rows
         (plan_filter_groups); with config.filter_query_masks the groups left to the masked scan
-        share one dense scan per 64 queries, each query under its own mask. The answers do not
+        share one dense scan per 64 queries, each query under its own mask, and with
+        config.filter_query_masks_sparse one sparse search per call as well. The answers do not
         depend on the path, only TopK.flags tell (ARMI_FLAG_ROWLIST, ARMI_FLAG_QMASK). With
         num_gpus > 1 the knobs are ignored and the list form refused."""
         resolved = self._ensure_collection(collection_name)
@@ -462,7 +472,8 @@ class MI355XRetriever(BaseRetriever):
                                     lambda f: coll.segment_row_lists(f, knob)[2],
                                     query_masks=self.config.filter_query_masks, mode=mode,
                                     tail_rows=tail_rows,
-                                    qmask_supported=lambda n: seg.dense.qmask_supported(n, leg_k))
+                                    qmask_supported=lambda n: seg.dense.qmask_supported(n, leg_k),
+                                    sparse_masks=self.config.filter_query_masks_sparse)
         self.last_plan = groups
         if len(groups) == 1 and not groups[0].rowlist:  # one masked search, as without a plan
             return self._search_device(coll, queries, top_k, mode,
@@ -579,9 +590,11 @@ class MI355XRetriever(BaseRetriever):
     def _search_qmask(self, coll: ChunkCollection, seg, queries: QueryBatch, top_k: int, mode: str,
                       filters: list, q_mask: list) -> TopK:
         """One qmask_calls call (<= 128 queries, in that call's order): the dense leg is one
-        DenseIndex.topk_masks over the stacked masks of `filters`; hybrid's sparse leg stays one
-        masked SparseIndex.topk per distinct filter, scattered into the call's order, and one RRF
-        fuses the two legs for the whole call (RRF is per query). No tail rows (the planner)."""
+        DenseIndex.topk_masks over the stacked masks of `filters`, mode sparse one
+        SparseIndex.topk_masks over them. Hybrid's sparse leg is that call too with
+        config.filter_query_masks_sparse, else one masked SparseIndex.topk per distinct filter,
+        scattered into the call's order; one RRF fuses the two legs for the whole call (RRF is per
+        query). No tail rows (the planner)."""
         dev = self.device
         masks = [coll.filter_mask(f) for f in filters]
         words = max((seg.dense.n_rows + 63) // 64, 1)
@@ -592,8 +605,20 @@ class MI355XRetriever(BaseRetriever):
         def dense(k: int) -> TopK:
             return seg.dense.topk_masks(queries.dense, k, stacked, qm)
 
+        sq = (queries.sparse_indptr, queries.sparse_indices, queries.sparse_values)
+
+        def sparse_masks(k: int) -> TopK:
+            return seg.sparse.topk_masks(*sq, k, stacked, qm)
+
+        if mode == "sparse":
+            return sparse_masks(top_k)
         if mode != "hybrid":
             return dense(top_k)
+        if self._hybrid is None:
+            self._hybrid = ConcurrentHybrid(self.device)
+        if self.config.filter_query_masks_sparse:
+            return self._hybrid(lambda: dense(2 * top_k), lambda: sparse_masks(2 * top_k),
+                                sq + (stacked, qm), top_k, rrf_k=self.config.rrf_k)
         by_mask: dict = {}
         for i, m in enumerate(q_mask):
             by_mask.setdefault(m, []).append(i)
@@ -607,9 +632,6 @@ class MI355XRetriever(BaseRetriever):
                 parts.append((idx, s, 0))
             return self._scatter(parts, len(q_mask))
 
-        if self._hybrid is None:
-            self._hybrid = ConcurrentHybrid(self.device)
-        sq = (queries.sparse_indptr, queries.sparse_indices, queries.sparse_values)
         return self._hybrid(lambda: dense(2 * top_k), lambda: sparse(2 * top_k),
                             sq + tuple(masks), top_k, rrf_k=self.config.rrf_k)
 

@@ -60,7 +60,7 @@ extern "C" {
  * 4: row-list top-k (armi_dense_rowlist_topk, armi_sparse_rowlist_topk, ARMI_FLAG_ROWLIST);
  * nothing removed. 5: armi_sparse_tail_topk (+ _workspace_bytes, _chunk_rows); nothing removed.
  * 6: per-query row masks (armi_dense_topk_qmask, + _supported, _workspace_bytes,
- * ARMI_FLAG_QMASK); nothing removed. */
+ * armi_sparse_topk_qmask, ARMI_FLAG_QMASK); nothing removed. */
 #define ARMI_ABI_VERSION 6
 
 /* flags written per query by the top-k entry points */
@@ -70,8 +70,9 @@ extern "C" {
                                 * ARMI_FLAG_CERTIFIED) instead of the exact scan */
 #define ARMI_FLAG_ROWLIST 8u   /* answered by a row-list entry point (armi_*_rowlist_topk): the exact
                                 * ranking of the listed rows by construction, no certificate */
-#define ARMI_FLAG_QMASK 16u    /* answered by armi_dense_topk_qmask (one row mask per query), with
-                                * ARMI_FLAG_CERTIFIED or ARMI_FLAG_FALLBACK as armi_dense_topk */
+#define ARMI_FLAG_QMASK 16u    /* answered by armi_dense_topk_qmask or armi_sparse_topk_qmask (one row
+                                * mask per query), with the bits armi_dense_topk / armi_sparse_topk
+                                * set (CERTIFIED or FALLBACK; sparse also FILTERED) */
 
 const char* armi_last_error(void);
 int armi_abi_version(void);
@@ -421,6 +422,34 @@ int armi_sparse_topk(const armi_sparse_index* index, const int32_t* q_indptr,
                      const uint64_t* row_mask, float* out_scores, int64_t* out_ids,
                      int32_t* out_count, uint32_t* out_flags, void* workspace,
                      size_t workspace_bytes, hipStream_t stream);
+
+/* armi_sparse_topk in which every query carries its own row mask, in the same launches as one
+ * armi_sparse_topk call: the batch a server sees when it coalesces sparse or hybrid requests that
+ * each bring a payload filter of any selectivity (the reference takes one filter per request,
+ * src/audio_rag/api/v1/query.py:41, built at src/audio_rag/retrieval/qdrant.py:263-269, for
+ * every search type). The result of query q is bit for bit armi_sparse_topk's with row_mask =
+ * that query's mask: ids, fp32 scores, count and the -1 / -inf padding.
+ *   row_masks          uint64 [n_masks][mask_stride_words] bitmasks over the index's rows, bit r of
+ *                      mask m = row r (armi_sparse_topk's row_mask convention);
+ *                      mask_stride_words >= ceil(rows / 64). Bits past the last row are ignored.
+ *                      May be null when n_masks = 0.
+ *   q_mask             int32 [n_queries] (device): the mask of query q, or -1 for no filter. An
+ *                      entry outside [-1, n_masks) is TREATED AS -1 (the query is unfiltered); it
+ *                      never indexes row_masks. Several queries may share a mask.
+ * Covers everything armi_sparse_topk covers (any n_queries in passes of 64, k 1..240, the MFMA
+ * filter where the index allows it and the exact scan for the rest, ordinal_base), so there is
+ * no _supported call, and the workspace is armi_sparse_workspace_bytes(index, n_queries, k). Both
+ * scans walk the rows in ordinal order, so each kernel reads a (tile, query) mask word straight
+ * from row_masks: no mask image, no extra kernel. A null pointer, n_masks < 0, a short stride, k
+ * outside [1, 240] and a workspace that is too small return ARMI_ERR_INVALID before any device
+ * work. out_flags = armi_sparse_topk's bits | ARMI_FLAG_QMASK for every query.
+ * No host synchronisation; graph-capture safe. */
+int armi_sparse_topk_qmask(const armi_sparse_index* index, const int32_t* q_indptr,
+                           const int32_t* q_indices, const float* q_values, int n_queries, int k,
+                           const uint64_t* row_masks, int64_t mask_stride_words,
+                           const int32_t* q_mask, int n_masks, float* out_scores,
+                           int64_t* out_ids, int32_t* out_count, uint32_t* out_flags,
+                           void* workspace, size_t workspace_bytes, hipStream_t stream);
 
 /* Sparse dot-product top-k over given rows (armi_dense_rowlist_topk's list encoding: list_ptr,
  * list_rows, q_list, n_lists, max_list_rows), computed from the forward CSR the caller built the

@@ -19,7 +19,15 @@ the qmask scan kernel and of the mask-image kernel (armi_kernel_timing_read) bes
 int8 scan's, measured the same way. The result is merged into --out (JSON, one entry per row
 count).
 
+--sparse measures RetrievalConfig.filter_query_masks_sparse instead (DESIGN "Sparse search: one
+row mask per query"): the same collection, cases and protocol with mode sparse top-20 and hybrid
+40 + 40 -> 20; "off" is filter_query_masks alone (one masked sparse search per filter: what the
+code did before the sparse knob), "on" both knobs. Kernel times (ARMI_TIMING_SPARSE_SCAN, the MFMA
+filter scan of a 64-query pass at k = 20): sparse_filter_scan_kernel under one shared mask, its
+per-query sibling under (a)'s 64 masks, and the unmasked scan.
+
     python tools/filter_mask_bench.py --rows 100000 --out profiles/filter_masks.json
+    python tools/filter_mask_bench.py --sparse --rows 100000 --out profiles/sparse_query_masks.json
 """
 
 from __future__ import annotations
@@ -70,6 +78,8 @@ def main() -> None:
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default="profiles/filter_masks.json")
+    ap.add_argument("--sparse", action="store_true",
+                    help="measure filter_query_masks_sparse (sparse and hybrid cells)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("filter_mask_bench needs the GPU")
@@ -82,17 +92,19 @@ def main() -> None:
     sparse = SparseIndex(*synthetic.make_sparse_rows(0, n, dev), vocab=synthetic.VOCAB)
     coll = ChunkCollection.from_indexes("audio_rag", dense, payloads(n), sparse)
 
-    def retriever(masks: bool) -> MI355XRetriever:
-        r = MI355XRetriever(RetrievalConfig(filter_query_masks=masks, reproduce_sparse_drop=False,
-                                            query_graphs=False), dim)
+    def retriever(masks: bool, sparse_masks: bool = False) -> MI355XRetriever:
+        r = MI355XRetriever(RetrievalConfig(filter_query_masks=masks,
+                                            filter_query_masks_sparse=sparse_masks,
+                                            reproduce_sparse_drop=False, query_graphs=False), dim)
         r.attach_collection(coll)
         return r
 
-    off, on = retriever(False), retriever(True)
+    off, on = (retriever(True), retriever(True, True)) if args.sparse else \
+        (retriever(False), retriever(True))
     qd = synthetic.make_queries(1, B, dim, dev, seed=9)[0]
     qi, qx, qv = synthetic.make_sparse_queries(B, dev, seed=10)
     qb = QueryBatch(dense=qd, sparse_indptr=qi, sparse_indices=qx, sparse_values=qv)
-    modes = {"dense": 5, "hybrid": 20}
+    modes = {"sparse": 20, "hybrid": 20} if args.sparse else {"dense": 5, "hybrid": 20}
     broad = {"k0": 0}
     cases = {
         "a_64_distinct_filters": [{f"k{q // KEYS}": q % KEYS} for q in range(B)],
@@ -113,9 +125,48 @@ def main() -> None:
                                   args.warmup)
             entry[mode]["equal"] = same(x, y, mode)
             entry[mode]["qmask_groups"] = sum(g.qmask for g in on.last_plan)
-            if mode == "dense":
+            if mode in ("dense", "sparse"):
                 entry[mode]["qmask_queries"] = qmask_queries(y)
         res[name] = entry
+
+    if args.sparse:
+        # kernel launch times of the filter scan: one shared mask, (a)'s 64 masks, no mask
+        flt = cases["a_64_distinct_filters"]
+        k = modes["sparse"]
+        one = coll.filter_mask(broad)
+        stacked = torch.stack([coll.filter_mask(f) for f in flt])
+        qm = torch.arange(B, dtype=torch.int32, device=dev)
+        ws = torch.empty(sparse.workspace_bytes(B, k), dtype=torch.uint8, device=dev)
+        runs = {"masked_filter_scan": lambda: sparse.topk(qi, qx, qv, k, row_mask=one, workspace=ws),
+                "qmask_filter_scan": lambda: sparse.topk_masks(qi, qx, qv, k, stacked, qm,
+                                                               workspace=ws),
+                "unmasked_filter_scan": lambda: sparse.topk(qi, qx, qv, k, workspace=ws)}
+        # (period 2: a sparse call whose whole stage is timed does not time its scan; the two
+        # alternate)
+        _armi.call("armi_scan_timing_enable", 2)
+        kernel_ms(_armi.TIMING_SPARSE_SCAN)
+        reps = 10 * args.steps
+        times = {}
+        for name, fn in runs.items():
+            filtered = int(((fn().flags & _armi.ARMI_FLAG_FILTERED) != 0).sum())
+            kernel_ms(_armi.TIMING_SPARSE_SCAN)
+            for _ in range(reps):
+                fn()
+            total, launches = kernel_ms(_armi.TIMING_SPARSE_SCAN)
+            kernel_ms(_armi.TIMING_SPARSE_STAGE)
+            times[name] = total / max(launches, 1)
+            times[name + "_launches"] = launches
+            times[name + "_filtered_queries"] = filtered
+        _armi.call("armi_scan_timing_enable", 0)
+        times["qmask_over_masked_scan"] = times["qmask_filter_scan"] / times["masked_filter_scan"]
+        res["kernels_ms"] = times
+        out = Path(args.out)
+        merged = json.loads(out.read_text()) if out.exists() else {}
+        merged[str(n)] = res
+        out.parent.mkdir(parents=True, exist_ok=True)
+        out.write_text(json.dumps(merged, indent=1) + "\n")
+        print(json.dumps(res))
+        return
 
     # the dense legs of (a) and (b) as device work only, replayed from HIP graphs
     k = modes["dense"]
