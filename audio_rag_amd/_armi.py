@@ -51,6 +51,10 @@ SIGNATURES: dict[str, tuple] = {
     "armi_dense_tail_topk": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_size_t, c_void_p]),
+    "armi_dense_tail_topk_qmask": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64,
+                                           c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_size_t, c_void_p]),
     "armi_dense_rowlist_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int64]),
     "armi_dense_rowlist_topk": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                         c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -66,6 +70,11 @@ SIGNATURES: dict[str, tuple] = {
                                       c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_size_t, c_void_p]),
+    "armi_sparse_tail_topk_qmask": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
+                                            c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64,
+                                            c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_size_t, c_void_p]),
     "armi_dense_scan_form": (c_int, [c_void_p, c_int, c_int]),
     "armi_dense_scan_nontemporal": (c_int, [c_void_p, c_int, c_int]),
     "armi_index_destroy": (c_int, [c_void_p]),

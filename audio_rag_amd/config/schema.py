@@ -93,6 +93,14 @@ class RetrievalConfig(BaseModel):
     # search per filter. False: as before. Answers are the same either way. Ignored with
     # num_gpus > 1
     filter_query_masks_sparse: bool = False
+    # the same for a live collection with tail rows (live_tail_rows > 0 after an add): True lifts
+    # the "no tail rows" condition of whichever of the two knobs above is on, so the groups keep
+    # their one scan per call and the tail is covered by one fused tail pass in which every query
+    # carries its own mask over the tail's rows (armi_dense_tail_topk_qmask,
+    # armi_sparse_tail_topk_qmask). It changes nothing by itself. A knob of its own because the two
+    # above keep a collection with tail rows at one search per filter. False: as before. Answers
+    # are the same either way. Ignored with num_gpus > 1
+    filter_query_masks_live: bool = False
 
 
 class RerankingConfig(BaseModel):

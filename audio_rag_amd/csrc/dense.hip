@@ -3023,10 +3023,19 @@ constexpr int kTailWgRows = kTailTilesPerWg * TILE_ROWS;
 template <int DIM>
 constexpr int tail_scan_lds_bytes() { return scan_img_bytes<DIM>() + kQB * 8 + kWaves * kQB * 8; }
 
-template <int DIM>
-__global__ __launch_bounds__(kThreads) void dense_tail_scan_kernel(
+// QMASK (armi_dense_tail_topk_qmask): every query carries its own row filter, read straight from
+// the caller's masks. The tail is scanned in ordinal order, so the 32 rows of tile t are the 32-bit
+// word t of a mask row (uint64 word t / 2, its low half first); t < n_tiles <= 2 ceil(rows / 64)
+// <= 2 mask_stride, so the read stays inside the query's row of the stack. A lane keeps the mask
+// rows of its two queries (null: unfiltered: -1, an entry outside [0, n_masks), a query past the
+// batch, for which q_mask is not read), loads their words of a tile with the tile and tests the
+// row's bit together with >= thr. row_scales runs without a mask; bits of padding and invalid rows
+// do nothing, their scale is NaN.
+template <int DIM, bool QMASK>
+__device__ __forceinline__ void dense_tail_scan_body(
     const uint16_t* __restrict__ rows, const float* __restrict__ inv_norm32,
-    const uint64_t* __restrict__ row_mask, int64_t n_rows, int64_t n_tiles,
+    const uint64_t* __restrict__ row_mask, const int32_t* __restrict__ q_mask, int n_masks,
+    int64_t mask_stride, int64_t n_rows, int64_t n_tiles,
     const uint16_t* __restrict__ queries_all, int nq_all, int k,
     const double* __restrict__ main_rank, const int32_t* __restrict__ main_count,
     int32_t* __restrict__ wg_cnt, int32_t* __restrict__ wg_list) {
@@ -3095,11 +3104,30 @@ __global__ __launch_bounds__(kThreads) void dense_tail_scan_kernel(
   const float thr0 = s_thr[r], thr1 = s_thr[32 + r];
   int32_t* list0 = wg_list + ((size_t)(q0 + r) * n_wg + blockIdx.x) * kTailWgRows;
   int32_t* list1 = wg_list + ((size_t)(q0 + 32 + r) * n_wg + blockIdx.x) * kTailWgRows;
+  // QMASK: the mask rows of the lane's two queries as 32-bit words
+  const uint32_t* mrow0 = nullptr;
+  const uint32_t* mrow1 = nullptr;
+  if constexpr (QMASK) {
+    auto mask_words = [&](int ql) -> const uint32_t* {
+      if (ql >= nq) return nullptr;
+      const int32_t m = q_mask[q0 + ql];
+      return m >= 0 && m < n_masks
+                 ? reinterpret_cast<const uint32_t*>(row_mask + (int64_t)m * mask_stride)
+                 : nullptr;
+    };
+    mrow0 = mask_words(r);
+    mrow1 = mask_words(32 + r);
+  }
 
   for (; t < t_end; t += kWaves) {
     const int64_t tn = (t + kWaves < t_end) ? t + kWaves : t_begin;
     const u32x4* nxt = row_ptr(tn);
     const int64_t row0 = t * TILE_ROWS;
+    uint32_t mk0 = ~0u, mk1 = ~0u;  // QMASK: the tile's mask words of the lane's two queries
+    if constexpr (QMASK) {            // (in flight across the tile's k-loop)
+      if (mrow0) mk0 = mrow0[t];
+      if (mrow1) mk1 = mrow1[t];
+    }
     f32x16 acc0, acc1;
     float4 iv4[4];
     fp16_tile_mma<DIM>(buf, cur, nxt, qimg, h, r, inv_norm32 + row0, iv4, acc0, acc1);
@@ -3109,16 +3137,25 @@ __global__ __launch_bounds__(kThreads) void dense_tail_scan_kernel(
     // invalid and filtered rows have a NaN scale, and NaN >= thr is false.
     // (A (row, query) pair is seen once, so a workgroup's list takes at most its kTailWgRows rows.)
     float inv[16];
-    row_scales(iv4, row_mask, row0, h, inv);
+    row_scales(iv4, QMASK ? nullptr : row_mask, row0, h, inv);
     const int32_t rbase = (int32_t)row0 + 4 * h;
+    if constexpr (QMASK) {  // the lane's rows are bits (j&3) + 8*(j>>2) + 4*h of the words
+      mk0 >>= 4 * h;
+      mk1 >>= 4 * h;
+    }
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
       const int32_t row = rbase + (j & 3) + 8 * (j >> 2);
-      if (acc0[j] * inv[j] >= thr0) {
+      bool on0 = acc0[j] * inv[j] >= thr0, on1 = acc1[j] * inv[j] >= thr1;
+      if constexpr (QMASK) {
+        on0 = on0 && ((mk0 >> ((j & 3) + 8 * (j >> 2))) & 1u);
+        on1 = on1 && ((mk1 >> ((j & 3) + 8 * (j >> 2))) & 1u);
+      }
+      if (on0) {
         const int slot = atomicAdd(s_cnt + r, 1);
         if (slot < kTailWgRows) list0[slot] = row;
       }
-      if (acc1[j] * inv[j] >= thr1) {
+      if (on1) {
         const int slot = atomicAdd(s_cnt + 32 + r, 1);
         if (slot < kTailWgRows) list1[slot] = row;
       }
@@ -3129,16 +3166,45 @@ __global__ __launch_bounds__(kThreads) void dense_tail_scan_kernel(
     wg_cnt[(size_t)(q0 + threadIdx.x) * n_wg + blockIdx.x] = min(s_cnt[threadIdx.x], kTailWgRows);
 }
 
+template <int DIM>
+__global__ __launch_bounds__(kThreads) void dense_tail_scan_kernel(
+    const uint16_t* __restrict__ rows, const float* __restrict__ inv_norm32,
+    const uint64_t* __restrict__ row_mask, int64_t n_rows, int64_t n_tiles,
+    const uint16_t* __restrict__ queries_all, int nq_all, int k,
+    const double* __restrict__ main_rank, const int32_t* __restrict__ main_count,
+    int32_t* __restrict__ wg_cnt, int32_t* __restrict__ wg_list) {
+  dense_tail_scan_body<DIM, false>(rows, inv_norm32, row_mask, nullptr, 0, 0, n_rows, n_tiles,
+                                   queries_all, nq_all, k, main_rank, main_count, wg_cnt, wg_list);
+}
+
+// the per-query-mask sibling (armi_dense_tail_topk_qmask)
+template <int DIM>
+__global__ __launch_bounds__(kThreads) void dense_tail_scan_qmask_kernel(
+    const uint16_t* __restrict__ rows, const float* __restrict__ inv_norm32,
+    const uint64_t* __restrict__ row_masks, const int32_t* __restrict__ q_mask, int n_masks,
+    int64_t mask_stride, int64_t n_rows, int64_t n_tiles,
+    const uint16_t* __restrict__ queries_all, int nq_all, int k,
+    const double* __restrict__ main_rank, const int32_t* __restrict__ main_count,
+    int32_t* __restrict__ wg_cnt, int32_t* __restrict__ wg_list) {
+  dense_tail_scan_body<DIM, true>(rows, inv_norm32, row_masks, q_mask, n_masks, mask_stride, n_rows,
+                                  n_tiles, queries_all, nq_all, k, main_rank, main_count, wg_cnt,
+                                  wg_list);
+}
+
 // LDS of dense_tail_finish_kernel: collect_top_rows' sort arrays, the gathered survivor rows, one
 // chunk of workgroup counts / offsets, the total.
 constexpr size_t kTailSortLds = 2 * kTailCap * 16;  // (key, ordinal) x (survivors + main list)
 constexpr size_t kTailFinishLds = kTailSortLds + kTailCap * 4 + 64 * 8 + 16;
 
-template <int DIM>
-__global__ __launch_bounds__(kDenseMergeThreads) void dense_tail_finish_kernel(
+// QMASK: row_mask is the call's [n_masks][mask_stride] stack; the exhaustive pass of an overflowed
+// query filters by that query's own row (the workgroup serves one query: workgroup-uniform), the
+// survivors were filtered by the scan, and every flag word gets ARMI_FLAG_QMASK.
+template <int DIM, bool QMASK>
+__device__ __forceinline__ void dense_tail_finish_body(
     const int32_t* __restrict__ wg_cnt, const int32_t* __restrict__ wg_list, int n_wg,
     const uint16_t* __restrict__ rows, const double* __restrict__ inv_norm,
-    const int64_t* __restrict__ norm2, const uint64_t* __restrict__ row_mask, int64_t n_rows,
+    const int64_t* __restrict__ norm2, const uint64_t* __restrict__ row_mask,
+    const int32_t* __restrict__ q_mask, int n_masks, int64_t mask_stride, int64_t n_rows,
     const uint16_t* __restrict__ queries, int k, int64_t ordinal_base,
     const int64_t* __restrict__ main_ids, const double* __restrict__ main_rank,
     const int32_t* __restrict__ main_count, float* __restrict__ out_scores,
@@ -3213,7 +3279,12 @@ __global__ __launch_bounds__(kDenseMergeThreads) void dense_tail_finish_kernel(
     // More than kTailCap survivors means more than kTailCap rows, so the rows take the chunked
     // path of collect_top_rows, which leaves the best kColChunk of them in front.
     static_assert(kTailCap >= kColChunk, "an overflowed tail is longer than one collect chunk");
-    collect_top_rows<DIM>(nullptr, 0, n_rows, k, qf, rows, inv_norm, norm2, row_mask, ordinal_base,
+    const uint64_t* mrow = row_mask;
+    if constexpr (QMASK) {
+      const int32_t m = q_mask[qg];
+      mrow = m >= 0 && m < n_masks ? row_mask + (int64_t)m * mask_stride : nullptr;
+    }
+    collect_top_rows<DIM>(nullptr, 0, n_rows, k, qf, rows, inv_norm, norm2, mrow, ordinal_base,
                           key, ord);
     p = kColChunk;
   }
@@ -3228,7 +3299,43 @@ __global__ __launch_bounds__(kDenseMergeThreads) void dense_tail_finish_kernel(
   armi::lds_sort_rank_desc(key, ord, 2 * p);
   armi::write_top_k(key, ord, qg, k, armi::ScoreTimes{iq}, out_scores, out_ids, out_rank,
                     out_count);
-  if (tid == 0) out_flags[qg] = overflow ? ARMI_FLAG_FALLBACK : ARMI_FLAG_CERTIFIED;
+  if (tid == 0)
+    out_flags[qg] = (overflow ? ARMI_FLAG_FALLBACK : ARMI_FLAG_CERTIFIED) |
+                    (QMASK ? ARMI_FLAG_QMASK : 0u);
+}
+
+template <int DIM>
+__global__ __launch_bounds__(kDenseMergeThreads) void dense_tail_finish_kernel(
+    const int32_t* __restrict__ wg_cnt, const int32_t* __restrict__ wg_list, int n_wg,
+    const uint16_t* __restrict__ rows, const double* __restrict__ inv_norm,
+    const int64_t* __restrict__ norm2, const uint64_t* __restrict__ row_mask, int64_t n_rows,
+    const uint16_t* __restrict__ queries, int k, int64_t ordinal_base,
+    const int64_t* __restrict__ main_ids, const double* __restrict__ main_rank,
+    const int32_t* __restrict__ main_count, float* __restrict__ out_scores,
+    int64_t* __restrict__ out_ids, double* __restrict__ out_rank, int32_t* __restrict__ out_count,
+    uint32_t* __restrict__ out_flags) {
+  dense_tail_finish_body<DIM, false>(wg_cnt, wg_list, n_wg, rows, inv_norm, norm2, row_mask, nullptr,
+                                     0, 0, n_rows, queries, k, ordinal_base, main_ids, main_rank,
+                                     main_count, out_scores, out_ids, out_rank, out_count,
+                                     out_flags);
+}
+
+// the per-query-mask sibling (armi_dense_tail_topk_qmask)
+template <int DIM>
+__global__ __launch_bounds__(kDenseMergeThreads) void dense_tail_finish_qmask_kernel(
+    const int32_t* __restrict__ wg_cnt, const int32_t* __restrict__ wg_list, int n_wg,
+    const uint16_t* __restrict__ rows, const double* __restrict__ inv_norm,
+    const int64_t* __restrict__ norm2, const uint64_t* __restrict__ row_masks,
+    const int32_t* __restrict__ q_mask, int n_masks, int64_t mask_stride, int64_t n_rows,
+    const uint16_t* __restrict__ queries, int k, int64_t ordinal_base,
+    const int64_t* __restrict__ main_ids, const double* __restrict__ main_rank,
+    const int32_t* __restrict__ main_count, float* __restrict__ out_scores,
+    int64_t* __restrict__ out_ids, double* __restrict__ out_rank, int32_t* __restrict__ out_count,
+    uint32_t* __restrict__ out_flags) {
+  dense_tail_finish_body<DIM, true>(wg_cnt, wg_list, n_wg, rows, inv_norm, norm2, row_masks, q_mask,
+                                    n_masks, mask_stride, n_rows, queries, k, ordinal_base, main_ids,
+                                    main_rank, main_count, out_scores, out_ids, out_rank, out_count,
+                                    out_flags);
 }
 
 // ARMI_TAIL_PASS=general forces armi_dense_tail_topk's general path (armi_dense_topk over the tail,
@@ -3605,6 +3712,57 @@ int armi_dense_tail_topk(const armi_index* tail, const uint16_t* queries, int n_
         tail_row_mask, tail->n_rows, queries, k, tail->ordinal_base, main_ids, main_rank,
         main_count, out_scores, out_ids, out_rank, out_count, out_flags);
     ARMI_LAUNCHED("dense_tail_finish_kernel");
+    return ARMI_OK;
+  });
+}
+
+int armi_dense_tail_topk_qmask(const armi_index* tail, const uint16_t* queries, int n_queries,
+                               int k, const uint64_t* tail_row_masks, int64_t mask_stride_words,
+                               const int32_t* q_mask, int n_masks, const float* main_scores,
+                               const int64_t* main_ids, const double* main_rank,
+                               const int32_t* main_count, float* out_scores, int64_t* out_ids,
+                               double* out_rank, int32_t* out_count, uint32_t* out_flags,
+                               void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  // (what needs no index first, so that those answers do not depend on the others)
+  ARMI_REQUIRE(n_masks >= 0, "armi_dense_tail_topk_qmask: n_masks < 0");
+  ARMI_REQUIRE(mask_stride_words >= 0, "armi_dense_tail_topk_qmask: mask_stride_words < 0");
+  ARMI_REQUIRE(k >= 1 && k <= kMaxK, "armi_dense_tail_topk_qmask: k must be in [1, 240]");
+  ARMI_REQUIRE(n_queries >= 0, "armi_dense_tail_topk_qmask: n_queries < 0");
+  ARMI_REQUIRE(tail != nullptr, "armi_dense_tail_topk_qmask: index is null");
+  ARMI_REQUIRE(mask_stride_words >= (tail->n_rows + 63) / 64,
+               "armi_dense_tail_topk_qmask: mask_stride_words < ceil(rows / 64)");
+  if (n_queries == 0) return ARMI_OK;
+  ARMI_REQUIRE(queries && q_mask && (tail_row_masks || n_masks == 0) && main_scores && main_ids &&
+                   main_rank && main_count && out_scores && out_ids && out_count && out_flags &&
+                   workspace,
+               "armi_dense_tail_topk_qmask: null pointer argument");
+  ARMI_REQUIRE(workspace_bytes >= armi_dense_tail_workspace_bytes(tail, n_queries, k),
+               "armi_dense_tail_topk_qmask: workspace too small");
+  ARMI_REQUIRE(out_scores != main_scores && out_ids != main_ids && out_rank != main_rank &&
+                   out_count != main_count,
+               "armi_dense_tail_topk_qmask: outputs must not alias the main list");
+  ARMI_HIP(hipSetDevice(tail->device));
+  const TailWorkspace w = carve_tail(workspace, tail, n_queries, k);
+  const int nq = n_queries;
+  return dispatch_dim(tail->dim, [&](auto D) {
+    constexpr int DIM = decltype(D)::value;
+    const int n_wg = tail_wgs(tail, false);
+    if (tail->n_rows > 0) {
+      if (int rc = allow_lds(dense_tail_scan_qmask_kernel<DIM>, tail_scan_lds_bytes<DIM>()))
+        return rc;
+      dense_tail_scan_qmask_kernel<DIM><<<dim3(n_wg, (nq + kQB - 1) / kQB), dim3(kThreads),
+                                          tail_scan_lds_bytes<DIM>(), stream>>>(
+          tail->rows, tail->inv_norm32, tail_row_masks, q_mask, n_masks, mask_stride_words,
+          tail->n_rows, tail->n_tiles, queries, nq, k, main_rank, main_count, w.wg_cnt, w.wg_list);
+      ARMI_LAUNCHED("dense_tail_scan_qmask_kernel");
+    }
+    dense_tail_finish_qmask_kernel<DIM><<<dim3(nq), dim3(kDenseMergeThreads), kTailFinishLds,
+                                          stream>>>(
+        w.wg_cnt, w.wg_list, tail->n_rows > 0 ? n_wg : 0, tail->rows, tail->inv_norm, tail->norm2,
+        tail_row_masks, q_mask, n_masks, mask_stride_words, tail->n_rows, queries, k,
+        tail->ordinal_base, main_ids, main_rank, main_count, out_scores, out_ids, out_rank,
+        out_count, out_flags);
+    ARMI_LAUNCHED("dense_tail_finish_qmask_kernel");
     return ARMI_OK;
   });
 }

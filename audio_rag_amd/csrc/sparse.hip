@@ -2169,12 +2169,16 @@ __device__ __forceinline__ void tail_load_main(double* key, int64_t* ord,
   }
 }
 
-__global__ __launch_bounds__(kStThreads) void sparse_tail_scan_kernel(
+// kQM (armi_sparse_tail_topk_qmask): row_mask_arg is the call's stack of masks and the workgroup,
+// which serves one query, filters by that query's row of it (qmask_row: none for -1 and for an
+// entry outside [0, n_masks)).
+template <bool kQM>
+__device__ __forceinline__ void sparse_tail_scan_body(
     const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
     const float* __restrict__ values, int64_t tail_rows, int64_t ordinal_base,
     const int32_t* __restrict__ q_indptr, const int32_t* __restrict__ q_indices,
-    const float* __restrict__ q_values, int k, const uint64_t* __restrict__ row_mask,
-    const float* __restrict__ main_scores, const int64_t* __restrict__ main_ids,
+    const float* __restrict__ q_values, int k, const uint64_t* __restrict__ row_mask_arg,
+    const QMask qm, const float* __restrict__ main_scores, const int64_t* __restrict__ main_ids,
     const int32_t* __restrict__ main_count, const uint32_t* __restrict__ main_flags, int direct,
     int kc, int32_t* __restrict__ part_cnt, double* __restrict__ part_key,
     int64_t* __restrict__ part_ord, float* __restrict__ out_scores,
@@ -2189,6 +2193,7 @@ __global__ __launch_bounds__(kStThreads) void sparse_tail_scan_kernel(
   __shared__ double key[kStSort];
   __shared__ int64_t ord[kStSort];
   const int q = blockIdx.y;
+  const uint64_t* __restrict__ row_mask = kQM ? qmask_row(row_mask_arg, qm, q) : row_mask_arg;
   const int chunk = blockIdx.x;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -2312,6 +2317,41 @@ __global__ __launch_bounds__(kStThreads) void sparse_tail_scan_kernel(
   }
 }
 
+__global__ __launch_bounds__(kStThreads) void sparse_tail_scan_kernel(
+    const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
+    const float* __restrict__ values, int64_t tail_rows, int64_t ordinal_base,
+    const int32_t* __restrict__ q_indptr, const int32_t* __restrict__ q_indices,
+    const float* __restrict__ q_values, int k, const uint64_t* __restrict__ row_mask,
+    const float* __restrict__ main_scores, const int64_t* __restrict__ main_ids,
+    const int32_t* __restrict__ main_count, const uint32_t* __restrict__ main_flags, int direct,
+    int kc, int32_t* __restrict__ part_cnt, double* __restrict__ part_key,
+    int64_t* __restrict__ part_ord, float* __restrict__ out_scores,
+    int64_t* __restrict__ out_ids, int32_t* __restrict__ out_count,
+    uint32_t* __restrict__ out_flags) {
+  sparse_tail_scan_body<false>(indptr, indices, values, tail_rows, ordinal_base, q_indptr,
+                               q_indices, q_values, k, row_mask, QMask{}, main_scores, main_ids,
+                               main_count, main_flags, direct, kc, part_cnt, part_key, part_ord,
+                               out_scores, out_ids, out_count, out_flags);
+}
+
+// the per-query-mask sibling (armi_sparse_tail_topk_qmask)
+__global__ __launch_bounds__(kStThreads) void sparse_tail_scan_qmask_kernel(
+    const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
+    const float* __restrict__ values, int64_t tail_rows, int64_t ordinal_base,
+    const int32_t* __restrict__ q_indptr, const int32_t* __restrict__ q_indices,
+    const float* __restrict__ q_values, int k, const uint64_t* __restrict__ row_masks,
+    const QMask qm, const float* __restrict__ main_scores, const int64_t* __restrict__ main_ids,
+    const int32_t* __restrict__ main_count, const uint32_t* __restrict__ main_flags, int direct,
+    int kc, int32_t* __restrict__ part_cnt, double* __restrict__ part_key,
+    int64_t* __restrict__ part_ord, float* __restrict__ out_scores,
+    int64_t* __restrict__ out_ids, int32_t* __restrict__ out_count,
+    uint32_t* __restrict__ out_flags) {
+  sparse_tail_scan_body<true>(indptr, indices, values, tail_rows, ordinal_base, q_indptr, q_indices,
+                              q_values, k, row_masks, qm, main_scores, main_ids, main_count,
+                              main_flags, direct, kc, part_cnt, part_key, part_ord, out_scores,
+                              out_ids, out_count, out_flags);
+}
+
 // One workgroup per query: [0, k) holds the best so far (first the main list), the chunk lists'
 // entries are gathered behind it, kStFinish - k at a time, and one bitonic sort per round keeps
 // the best k in front. The counts of kStGroup chunks are prefix-summed together so that the
@@ -2385,6 +2425,47 @@ __global__ __launch_bounds__(kStThreads) void sparse_tail_finish_kernel(
 }
 
 int64_t tail_chunks(int64_t tail_rows) { return (tail_rows + kStChunk - 1) / kStChunk; }
+
+// The launches of armi_sparse_tail_topk (q_mask null: row_masks is the call's one mask or null)
+// and armi_sparse_tail_topk_qmask; arguments checked by the entry points.
+int sparse_tail_launch(const int64_t* indptr, const int32_t* indices, const float* values,
+                       int64_t tail_rows, int64_t ordinal_base, const int32_t* q_indptr,
+                       const int32_t* q_indices, const float* q_values, int n_queries, int k,
+                       const uint64_t* row_masks, int64_t mask_stride, const int32_t* q_mask,
+                       int n_masks, const float* main_scores, const int64_t* main_ids,
+                       const int32_t* main_count, const uint32_t* main_flags, float* out_scores,
+                       int64_t* out_ids, int32_t* out_count, uint32_t* out_flags, void* workspace,
+                       hipStream_t stream) {
+  const int chunks = (int)tail_chunks(tail_rows);
+  const int direct = chunks == 1;
+  const int kc = std::min(k, kStChunk);
+  armi::Carver cv(workspace);
+  int32_t* part_cnt = cv.take<int32_t>(chunks > 1 ? (size_t)n_queries * chunks : 0);
+  double* part_key = cv.take<double>(chunks > 1 ? (size_t)n_queries * chunks * kc : 0);
+  int64_t* part_ord = cv.take<int64_t>(chunks > 1 ? (size_t)n_queries * chunks * kc : 0);
+  if (chunks > 0) {
+    if (q_mask) {
+      sparse_tail_scan_qmask_kernel<<<dim3(chunks, n_queries), dim3(kStThreads), 0, stream>>>(
+          indptr, indices, values, tail_rows, ordinal_base, q_indptr, q_indices, q_values, k,
+          row_masks, QMask{q_mask, mask_stride, n_masks, n_queries}, main_scores, main_ids,
+          main_count, main_flags, direct, kc, part_cnt, part_key, part_ord, out_scores, out_ids,
+          out_count, out_flags);
+      ARMI_LAUNCHED("sparse_tail_scan_qmask_kernel");
+    } else {
+      sparse_tail_scan_kernel<<<dim3(chunks, n_queries), dim3(kStThreads), 0, stream>>>(
+          indptr, indices, values, tail_rows, ordinal_base, q_indptr, q_indices, q_values, k,
+          row_masks, main_scores, main_ids, main_count, main_flags, direct, kc, part_cnt,
+          part_key, part_ord, out_scores, out_ids, out_count, out_flags);
+      ARMI_LAUNCHED("sparse_tail_scan_kernel");
+    }
+    if (direct) return ARMI_OK;
+  }
+  sparse_tail_finish_kernel<<<dim3(n_queries), dim3(kStThreads), 0, stream>>>(
+      part_cnt, part_key, part_ord, chunks, kc, k, main_scores, main_ids, main_count, main_flags,
+      out_scores, out_ids, out_count, out_flags);
+  ARMI_LAUNCHED("sparse_tail_finish_kernel");
+  return ARMI_OK;
+}
 
 }  // namespace
 
@@ -2476,26 +2557,45 @@ int armi_sparse_tail_topk(const int64_t* indptr, const int32_t* indices, const f
                "armi_sparse_tail_topk: workspace too small");
   ARMI_REQUIRE(out_scores != main_scores && out_ids != main_ids && out_count != main_count,
                "armi_sparse_tail_topk: outputs must not alias the main list");
-  const int chunks = (int)tail_chunks(tail_rows);
-  const int direct = chunks == 1;
-  const int kc = std::min(k, kStChunk);
-  armi::Carver cv(workspace);
-  int32_t* part_cnt = cv.take<int32_t>(chunks > 1 ? (size_t)n_queries * chunks : 0);
-  double* part_key = cv.take<double>(chunks > 1 ? (size_t)n_queries * chunks * kc : 0);
-  int64_t* part_ord = cv.take<int64_t>(chunks > 1 ? (size_t)n_queries * chunks * kc : 0);
-  if (chunks > 0) {
-    sparse_tail_scan_kernel<<<dim3(chunks, n_queries), dim3(kStThreads), 0, stream>>>(
-        indptr, indices, values, tail_rows, ordinal_base, q_indptr, q_indices, q_values, k,
-        tail_row_mask, main_scores, main_ids, main_count, main_flags, direct, kc, part_cnt,
-        part_key, part_ord, out_scores, out_ids, out_count, out_flags);
-    ARMI_LAUNCHED("sparse_tail_scan_kernel");
-    if (direct) return ARMI_OK;
-  }
-  sparse_tail_finish_kernel<<<dim3(n_queries), dim3(kStThreads), 0, stream>>>(
-      part_cnt, part_key, part_ord, chunks, kc, k, main_scores, main_ids, main_count, main_flags,
-      out_scores, out_ids, out_count, out_flags);
-  ARMI_LAUNCHED("sparse_tail_finish_kernel");
-  return ARMI_OK;
+  return sparse_tail_launch(indptr, indices, values, tail_rows, ordinal_base, q_indptr, q_indices,
+                            q_values, n_queries, k, tail_row_mask, 0, nullptr, 0, main_scores,
+                            main_ids, main_count, main_flags, out_scores, out_ids, out_count,
+                            out_flags, workspace, stream);
+}
+
+int armi_sparse_tail_topk_qmask(const int64_t* indptr, const int32_t* indices, const float* values,
+                                int64_t tail_rows, int64_t ordinal_base, const int32_t* q_indptr,
+                                const int32_t* q_indices, const float* q_values, int n_queries,
+                                int k, const uint64_t* tail_row_masks, int64_t mask_stride_words,
+                                const int32_t* q_mask, int n_masks, const float* main_scores,
+                                const int64_t* main_ids, const int32_t* main_count,
+                                const uint32_t* main_flags, float* out_scores, int64_t* out_ids,
+                                int32_t* out_count, uint32_t* out_flags, void* workspace,
+                                size_t workspace_bytes, hipStream_t stream) {
+  ARMI_REQUIRE(n_masks >= 0, "armi_sparse_tail_topk_qmask: n_masks < 0");
+  ARMI_REQUIRE(tail_rows >= 0, "armi_sparse_tail_topk_qmask: tail_rows < 0");
+  ARMI_REQUIRE(tail_chunks(tail_rows) <= 0x7fffffff,
+               "armi_sparse_tail_topk_qmask: tail_rows too large for one call");
+  ARMI_REQUIRE(mask_stride_words >= (tail_rows + 63) / 64,
+               "armi_sparse_tail_topk_qmask: mask_stride_words < ceil(tail_rows / 64)");
+  ARMI_REQUIRE(n_queries >= 0 && n_queries <= 65535,
+               "armi_sparse_tail_topk_qmask: n_queries must be in [0, 65535]");
+  ARMI_REQUIRE(k >= 1 && k <= kMaxK, "armi_sparse_tail_topk_qmask: k must be in [1, 240]");
+  if (n_queries == 0) return ARMI_OK;
+  // (nullable as in armi_sparse_tail_topk; the masks may be null when there are none)
+  ARMI_REQUIRE((indptr || tail_rows == 0) && q_indptr && q_mask &&
+                   (tail_row_masks || n_masks == 0) && main_scores && main_ids && main_count &&
+                   out_scores && out_ids && out_count,
+               "armi_sparse_tail_topk_qmask: null pointer argument");
+  const size_t need = armi_sparse_tail_workspace_bytes(tail_rows, n_queries, k);
+  ARMI_REQUIRE(workspace_bytes >= need && (workspace || need == 0),
+               "armi_sparse_tail_topk_qmask: workspace too small");
+  ARMI_REQUIRE(out_scores != main_scores && out_ids != main_ids && out_count != main_count,
+               "armi_sparse_tail_topk_qmask: outputs must not alias the main list");
+  return sparse_tail_launch(indptr, indices, values, tail_rows, ordinal_base, q_indptr, q_indices,
+                            q_values, n_queries, k, tail_row_masks, mask_stride_words, q_mask,
+                            n_masks, main_scores, main_ids, main_count, main_flags, out_scores,
+                            out_ids, out_count, out_flags, workspace, stream);
 }
 
 int armi_sparse_index_create(int device, const int64_t* indptr, const int32_t* indices,

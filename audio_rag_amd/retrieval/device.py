@@ -378,6 +378,34 @@ class TailIndex(DenseIndex):
              ptr(out.count), ptr(out.flags), ptr(workspace), workspace.numel(), stream_handle())
         return out
 
+    def tail_topk_masks(self, queries: torch.Tensor, k: int, main: TopK, row_masks: torch.Tensor,
+                        q_mask: torch.Tensor, workspace: torch.Tensor | None = None) -> TopK:
+        """tail_topk with one mask over this segment's rows per query, in the same two launches
+        (armi_dense_tail_topk_qmask): row_masks int64 [n_masks, words] device bitmasks (bit r =
+        row r of this segment), q_mask int32 [B] the mask of each query or -1 for none (a host
+        tensor is uploaded). `main` = the main index's list of the same queries and k, each query
+        under its own filter (DenseIndex.topk_masks). The same answer as tail_topk(row_mask=...)
+        called once per mask; flags carry ARMI_FLAG_QMASK. Any k that tail_topk takes."""
+        _check_fp16_2d(queries, "queries", self.dim)
+        _check_k(k)
+        b = int(queries.shape[0])
+        if tuple(main.ids.shape) != (b, k):
+            raise ValueError("main must be the main index's top-k of the same queries and k")
+        dev = self.device
+        n_masks, stride = _check_row_masks(row_masks, q_mask, b, self.n_rows)
+        q_mask = _on_device(q_mask, dev)
+        out = TopK.empty(b, k, dev, rank=True)
+        if b == 0:
+            return out
+        workspace = _workspace(workspace, self.tail_workspace_bytes(b, k), dev)
+        m_scores, m_ids, m_rank, m_count = (t.contiguous() for t in
+                                            (main.scores, main.ids, main.rank, main.count))
+        call("armi_dense_tail_topk_qmask", self._handle, ptr(queries), b, k,
+             ptr(row_masks) if n_masks else None, stride, ptr(q_mask), n_masks, ptr(m_scores),
+             ptr(m_ids), ptr(m_rank), ptr(m_count), ptr(out.scores), ptr(out.ids), ptr(out.rank),
+             ptr(out.count), ptr(out.flags), ptr(workspace), workspace.numel(), stream_handle())
+        return out
+
 
 class SparseIndex:
     """The Qdrant sparse vector "sparse" (SparseVectorParams(index=SparseIndexParams(on_disk=
@@ -610,16 +638,7 @@ class TailSparseIndex:
         b = int(q_indptr.numel()) - 1
         indptr, indices, values, n_rows = self._csr
         dev = indptr.device
-        for t, dt, shape, name in ((main.ids, torch.int64, (b, k), "ids"),
-                                   (main.scores, torch.float32, (b, k), "scores"),
-                                   (main.count, torch.int32, (b,), "count"),
-                                   (main.flags, torch.int32, (b,), "flags")):
-            if name == "flags" and t is None:
-                continue
-            if b < 0 or not isinstance(t, torch.Tensor) or t.dtype != dt or \
-                    tuple(t.shape) != shape or t.device != dev:
-                raise ValueError("main must be the main index's top-k of the same queries and k "
-                                 f"on {dev} (its {name} is not a {dt} tensor of shape {shape} there)")
+        self._check_main(main, b, k, dev)
         if q_indptr.device != dev:
             raise ValueError(f"the query CSR must live on {dev}")
         if row_mask is not None:
@@ -648,6 +667,56 @@ class TailSparseIndex:
                  ptr(row_mask), ptr(m_scores), ptr(m_ids), ptr(m_count), ptr(m_flags),
                  ptr(out.scores), ptr(out.ids), ptr(out.count), ptr(out.flags), ptr(workspace),
                  workspace.numel(), stream_handle())
+        return out
+
+    @staticmethod
+    def _check_main(main: TopK, b: int, k: int, dev: torch.device) -> None:
+        for t, dt, shape, name in ((main.ids, torch.int64, (b, k), "ids"),
+                                   (main.scores, torch.float32, (b, k), "scores"),
+                                   (main.count, torch.int32, (b,), "count"),
+                                   (main.flags, torch.int32, (b,), "flags")):
+            if name == "flags" and t is None:
+                continue
+            if b < 0 or not isinstance(t, torch.Tensor) or t.dtype != dt or \
+                    tuple(t.shape) != shape or t.device != dev:
+                raise ValueError("main must be the main index's top-k of the same queries and k "
+                                 f"on {dev} (its {name} is not a {dt} tensor of shape {shape} there)")
+
+    def tail_topk_masks(self, q_indptr: torch.Tensor, q_indices: torch.Tensor,
+                        q_values: torch.Tensor, k: int, main: TopK, row_masks: torch.Tensor,
+                        q_mask: torch.Tensor, workspace: torch.Tensor | None = None) -> TopK:
+        """tail_topk with one mask over this segment's rows per query, in the same launches
+        (armi_sparse_tail_topk_qmask): row_masks int64 [n_masks, words] device bitmasks (bit r =
+        row r of this segment), q_mask int32 [B] the mask of each query or -1 for none (a host
+        tensor is uploaded). `main` = the main SparseIndex's list of the same queries and k, each
+        query under its own filter (SparseIndex.topk_masks); its flags pass through. The same
+        answer as tail_topk(row_mask=...) called once per mask."""
+        _check_k(k)
+        _check_query_csr(q_indptr, q_indices, q_values)
+        b = int(q_indptr.numel()) - 1
+        indptr, indices, values, n_rows = self._csr
+        dev = indptr.device
+        self._check_main(main, b, k, dev)
+        if q_indptr.device != dev:
+            raise ValueError(f"the query CSR must live on {dev}")
+        n_masks, stride = _check_row_masks(row_masks, q_mask, b, n_rows)
+        if row_masks.device != dev:
+            raise ValueError(f"row_masks must live on {dev}")
+        q_mask = _on_device(q_mask, dev)
+        out = TopK.empty(b, k, dev, rank=False)
+        if b == 0:
+            return out
+        need = int(query("armi_sparse_tail_workspace_bytes", n_rows, b, k))
+        workspace = _workspace(workspace, need, dev)
+        m_scores, m_ids, m_count = (t.contiguous() for t in (main.scores, main.ids, main.count))
+        m_flags = None if main.flags is None else main.flags.contiguous()
+        with torch.cuda.device(dev):
+            call("armi_sparse_tail_topk_qmask", ptr(indptr), ptr(indices), ptr(values), n_rows,
+                 self.ordinal_base, ptr(q_indptr), ptr(q_indices), ptr(q_values), b, k,
+                 ptr(row_masks) if n_masks else None, stride, ptr(q_mask), n_masks, ptr(m_scores),
+                 ptr(m_ids), ptr(m_count), ptr(m_flags), ptr(out.scores), ptr(out.ids),
+                 ptr(out.count), ptr(out.flags), ptr(workspace), workspace.numel(),
+                 stream_handle())
         return out
 
     rowlist_workspace_bytes = staticmethod(SparseIndex.rowlist_workspace_bytes)

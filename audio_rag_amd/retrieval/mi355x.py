@@ -99,7 +99,8 @@ QMASK_MAX_QUERIES = 128  # queries of one armi_dense_topk_qmask call (sparse mod
 
 def plan_filter_groups(filters: list, n_rows: int, knob: int, count_matches,
                        query_masks: bool = False, mode: str = "dense", tail_rows: int = 0,
-                       qmask_supported=None, sparse_masks: bool = False) -> list[FilterGroup]:
+                       qmask_supported=None, sparse_masks: bool = False,
+                       tail_masks: bool = False) -> list[FilterGroup]:
     """Groups the queries of a batch by filter (in order of first appearance) and picks each
     group's path. A group of q queries whose filter matches m of the collection's n_rows rows is
     ranked from its row list iff the knob is on (filter_list_rows > 0), m <= knob and
@@ -114,14 +115,16 @@ def plan_filter_groups(filters: list, n_rows: int, knob: int, count_matches,
     their dense scans become one scan of the int8 image per 64 queries in which every query
     carries its own mask (DenseIndex.topk_masks). All of: query_masks (the filter_query_masks knob)
     on, at least two such groups (one group is one masked search already), mode dense /
-    legacy_dense / hybrid, no tail rows (the live tail pass has no such form) and
+    legacy_dense / hybrid, no tail rows unless tail_masks (the filter_query_masks_live knob: the
+    live tail pass then takes the masks too, TailIndex.tail_topk_masks) and
     qmask_supported(queries of a call) -> bool (the dense index's answer for the leg's k: an int8
     image, k <= 64). Otherwise they stay one masked search per group.
 
     Mode sparse has its own rule: sparse_masks (the filter_query_masks_sparse knob) on, at least
-    two such groups and no tail rows (armi_sparse_tail_topk takes one mask). The sparse form
-    (SparseIndex.topk_masks) has no shape limit, so neither query_masks nor qmask_supported is
-    consulted."""
+    two such groups and no tail rows unless tail_masks (armi_sparse_tail_topk takes one mask,
+    TailSparseIndex.tail_topk_masks one per query). The sparse form (SparseIndex.topk_masks) has no
+    shape limit, so neither query_masks nor qmask_supported is consulted. tail_masks alone marks
+    nothing."""
     groups: dict = {}
     for i, f in enumerate(filters):
         g = groups.get(filter_key(f))
@@ -133,13 +136,14 @@ def plan_filter_groups(filters: list, n_rows: int, knob: int, count_matches,
             g.matches = int(count_matches(g.filter))
             g.rowlist = g.matches <= knob and 2 * len(g.queries) * g.matches <= n_rows
     rest = [g for g in groups.values() if not g.rowlist]
-    if query_masks and len(rest) >= 2 and mode in QMASK_MODES and tail_rows == 0 and \
+    no_tail = tail_rows == 0 or tail_masks
+    if query_masks and len(rest) >= 2 and mode in QMASK_MODES and no_tail and \
             qmask_supported is not None:
         n = sum(len(g.queries) for g in rest)
         if qmask_supported(min(n, QMASK_MAX_QUERIES)):
             for g in rest:
                 g.qmask = True
-    if mode == "sparse" and sparse_masks and len(rest) >= 2 and tail_rows == 0:
+    if mode == "sparse" and sparse_masks and len(rest) >= 2 and no_tail:
         for g in rest:
             g.qmask = True
     return list(groups.values())
@@ -473,7 +477,8 @@ class MI355XRetriever(BaseRetriever):
                                     query_masks=self.config.filter_query_masks, mode=mode,
                                     tail_rows=tail_rows,
                                     qmask_supported=lambda n: seg.dense.qmask_supported(n, leg_k),
-                                    sparse_masks=self.config.filter_query_masks_sparse)
+                                    sparse_masks=self.config.filter_query_masks_sparse,
+                                    tail_masks=self.config.filter_query_masks_live)
         self.last_plan = groups
         if len(groups) == 1 and not groups[0].rowlist:  # one masked search, as without a plan
             return self._search_device(coll, queries, top_k, mode,
@@ -594,21 +599,32 @@ class MI355XRetriever(BaseRetriever):
         SparseIndex.topk_masks over them. Hybrid's sparse leg is that call too with
         config.filter_query_masks_sparse, else one masked SparseIndex.topk per distinct filter,
         scattered into the call's order; one RRF fuses the two legs for the whole call (RRF is per
-        query). No tail rows (the planner)."""
+        query). A collection with tail rows (the planner lets it in with
+        config.filter_query_masks_live) follows every main list with the fused tail pass over the
+        stacked tail masks (TailIndex / TailSparseIndex.tail_topk_masks), the per-filter sparse
+        searches with tail_topk under the filter's tail mask; an empty tail launches nothing."""
         dev = self.device
-        masks = [coll.filter_mask(f) for f in filters]
-        words = max((seg.dense.n_rows + 63) // 64, 1)
-        stacked = torch.stack(masks) if masks else torch.empty((0, words), dtype=torch.int64,
-                                                               device=dev)
+        live = seg.tail is not None and seg.tail.n_rows > 0
+        masks = [coll.segment_masks(f) for f in filters]  # (main, tail; tail None when not live)
+
+        def stack(which: int, n_rows: int) -> torch.Tensor:
+            if masks:
+                return torch.stack([m[which] for m in masks])
+            return torch.empty((0, max((n_rows + 63) // 64, 1)), dtype=torch.int64, device=dev)
+
+        stacked = stack(0, seg.dense.n_rows)
+        tstacked = stack(1, seg.tail.n_rows) if live else None
         qm = torch.tensor(q_mask, dtype=torch.int32, device=dev)
 
         def dense(k: int) -> TopK:
-            return seg.dense.topk_masks(queries.dense, k, stacked, qm)
+            d = seg.dense.topk_masks(queries.dense, k, stacked, qm)
+            return seg.tail.tail_topk_masks(queries.dense, k, d, tstacked, qm) if live else d
 
         sq = (queries.sparse_indptr, queries.sparse_indices, queries.sparse_values)
 
         def sparse_masks(k: int) -> TopK:
-            return seg.sparse.topk_masks(*sq, k, stacked, qm)
+            s = seg.sparse.topk_masks(*sq, k, stacked, qm)
+            return seg.tail_sparse.tail_topk_masks(*sq, k, s, tstacked, qm) if live else s
 
         if mode == "sparse":
             return sparse_masks(top_k)
@@ -616,9 +632,10 @@ class MI355XRetriever(BaseRetriever):
             return dense(top_k)
         if self._hybrid is None:
             self._hybrid = ConcurrentHybrid(self.device)
+        stacks = (stacked, qm) + ((tstacked,) if live else ())
         if self.config.filter_query_masks_sparse:
             return self._hybrid(lambda: dense(2 * top_k), lambda: sparse_masks(2 * top_k),
-                                sq + (stacked, qm), top_k, rrf_k=self.config.rrf_k)
+                                sq + stacks, top_k, rrf_k=self.config.rrf_k)
         by_mask: dict = {}
         for i, m in enumerate(q_mask):
             by_mask.setdefault(m, []).append(i)
@@ -627,13 +644,17 @@ class MI355XRetriever(BaseRetriever):
             parts = []
             for m, idx in by_mask.items():
                 sub = self._select(queries, idx)
-                s = seg.sparse.topk(sub.sparse_indptr, sub.sparse_indices, sub.sparse_values, k,
-                                    row_mask=None if m < 0 else masks[m])
+                sub_q = (sub.sparse_indptr, sub.sparse_indices, sub.sparse_values)
+                mask, tmask = (None, None) if m < 0 else masks[m]
+                s = seg.sparse.topk(*sub_q, k, row_mask=mask)
+                if live:
+                    s = seg.tail_sparse.tail_topk(*sub_q, k, s, row_mask=tmask)
                 parts.append((idx, s, 0))
             return self._scatter(parts, len(q_mask))
 
+        each = tuple(t for m in masks for t in m if t is not None)
         return self._hybrid(lambda: dense(2 * top_k), lambda: sparse(2 * top_k),
-                            sq + tuple(masks), top_k, rrf_k=self.config.rrf_k)
+                            sq + each + stacks, top_k, rrf_k=self.config.rrf_k)
 
     def _scatter(self, parts: list, b: int) -> TopK:
         """One TopK in query order from the groups' results: parts = (query indexes, TopK, flag

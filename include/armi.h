@@ -60,7 +60,8 @@ extern "C" {
  * 4: row-list top-k (armi_dense_rowlist_topk, armi_sparse_rowlist_topk, ARMI_FLAG_ROWLIST);
  * nothing removed. 5: armi_sparse_tail_topk (+ _workspace_bytes, _chunk_rows); nothing removed.
  * 6: per-query row masks (armi_dense_topk_qmask, + _supported, _workspace_bytes,
- * armi_sparse_topk_qmask, ARMI_FLAG_QMASK); nothing removed. */
+ * armi_sparse_topk_qmask, ARMI_FLAG_QMASK); nothing removed. Added since, version unchanged (a
+ * caller resolves them by name): armi_dense_tail_topk_qmask, armi_sparse_tail_topk_qmask. */
 #define ARMI_ABI_VERSION 6
 
 /* flags written per query by the top-k entry points */
@@ -197,6 +198,36 @@ int armi_dense_tail_topk(const armi_index* tail, const uint16_t* queries, int n_
                          const int32_t* main_count, float* out_scores, int64_t* out_ids,
                          double* out_rank, int32_t* out_count, uint32_t* out_flags,
                          void* workspace, size_t workspace_bytes, hipStream_t stream);
+
+/* armi_dense_tail_topk in which every query carries its own mask over the tail's rows, in the same
+ * two launches: the tail pass behind armi_dense_topk_qmask, for a live collection whose coalesced
+ * batch brings one payload filter per request. The answer of query q is bit for bit
+ * armi_dense_tail_topk's for the same main list with tail_row_mask = that query's mask (null for
+ * -1): ids, scores, rank keys, counts and the -1 / -inf padding.
+ *   tail_row_masks     uint64 [n_masks][mask_stride_words], bit r of mask m = tail row r;
+ *                      mask_stride_words >= ceil(tail rows / 64). Bits past the last row are
+ *                      ignored. May be null when n_masks = 0.
+ *   q_mask             int32 [n_queries] (device): the mask of query q, or -1 for no filter. An
+ *                      entry outside [-1, n_masks) is TREATED AS -1; it never indexes
+ *                      tail_row_masks. Read for queries < n_queries only.
+ * The main list is any finished list of the main index for the same queries and k
+ * (armi_dense_topk_qmask's, or armi_dense_topk's per mask for the k it does not serve). Every k in
+ * 1..240 and every n_queries armi_dense_tail_topk accepts; the workspace is
+ * armi_dense_tail_workspace_bytes(tail, n_queries, k). The tail is scanned in ordinal order, so the
+ * scan reads each (tile, query) mask word straight from tail_row_masks: no mask image, no extra
+ * kernel; an overflowed query's exhaustive pass filters by that query's own mask. out_flags =
+ * ARMI_FLAG_QMASK | (ARMI_FLAG_CERTIFIED or ARMI_FLAG_FALLBACK). A null pointer, n_masks < 0, a
+ * short stride, k outside [1, 240], a workspace that is too small and outputs that alias the main
+ * list return ARMI_ERR_INVALID before any device work. No host synchronisation; graph-capture
+ * safe. ARMI_TAIL_PASS=general does not apply to this call: its general path is armi_dense_topk
+ * over the tail, and armi_dense_topk_qmask does not run on a tail index. */
+int armi_dense_tail_topk_qmask(const armi_index* tail, const uint16_t* queries, int n_queries,
+                               int k, const uint64_t* tail_row_masks, int64_t mask_stride_words,
+                               const int32_t* q_mask, int n_masks, const float* main_scores,
+                               const int64_t* main_ids, const double* main_rank,
+                               const int32_t* main_count, float* out_scores, int64_t* out_ids,
+                               double* out_rank, int32_t* out_count, uint32_t* out_flags,
+                               void* workspace, size_t workspace_bytes, hipStream_t stream);
 
 /* Cosine top-k over given rows of the index instead of a masked scan of all of it: the search of
  * a selective metadata filter (Qdrant scores the matching points directly when a payload filter's
@@ -499,6 +530,27 @@ int armi_sparse_tail_topk(const int64_t* indptr, const int32_t* indices, const f
                           const uint32_t* main_flags, float* out_scores, int64_t* out_ids,
                           int32_t* out_count, uint32_t* out_flags, void* workspace,
                           size_t workspace_bytes, hipStream_t stream);
+
+/* armi_sparse_tail_topk in which every query carries its own mask over the tail's rows
+ * (tail_row_masks, mask_stride_words, q_mask, n_masks: armi_dense_tail_topk_qmask's conventions),
+ * in the same launches: the tail pass behind armi_sparse_topk_qmask. The answer of query q is bit
+ * for bit armi_sparse_tail_topk's for the same main list with tail_row_mask = that query's mask
+ * (null for -1, and for an entry outside [-1, n_masks), which never indexes tail_row_masks). A scan
+ * workgroup serves one query, so it filters by that query's row of the stack. Everything else as
+ * armi_sparse_tail_topk: k 1..240, n_queries <= 65535, _workspace_bytes(tail_rows, n_queries, k)
+ * (0 and a null pointer for a tail of one chunk), out_flags[q] = main_flags[q] (the main call
+ * armi_sparse_topk_qmask has set ARMI_FLAG_QMASK there). A null pointer, n_masks < 0, a short
+ * stride, k outside [1, 240], a workspace that is too small and outputs that alias the main list
+ * return ARMI_ERR_INVALID before any device work. No host synchronisation; graph-capture safe. */
+int armi_sparse_tail_topk_qmask(const int64_t* indptr, const int32_t* indices, const float* values,
+                                int64_t tail_rows, int64_t ordinal_base, const int32_t* q_indptr,
+                                const int32_t* q_indices, const float* q_values, int n_queries,
+                                int k, const uint64_t* tail_row_masks, int64_t mask_stride_words,
+                                const int32_t* q_mask, int n_masks, const float* main_scores,
+                                const int64_t* main_ids, const int32_t* main_count,
+                                const uint32_t* main_flags, float* out_scores, int64_t* out_ids,
+                                int32_t* out_count, uint32_t* out_flags, void* workspace,
+                                size_t workspace_bytes, hipStream_t stream);
 
 /* Enables (1) or disables (0) the MFMA filter of armi_sparse_topk on this index (default on:
  * the exact scan alone when off); usable (host, nullable) = 1 when the index can use the filter
