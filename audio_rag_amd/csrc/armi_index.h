@@ -99,4 +99,27 @@ struct armi_sparse_index {
 namespace armi {
 constexpr int TILE_ROWS = 32;
 constexpr float kTwoPow24 = 16777216.0f;
+
+// One row mask per query (the *_qmask entry points, dense and sparse): query q of the pass (q_mask
+// already points at the pass's first query) is filtered by row q_mask[q] of the caller's
+// [n_masks][stride] stack of ordinal bitmasks; -1, and any value outside [0, n_masks), is
+// unfiltered and indexes nothing; a query outside [0, nq) is unfiltered too, and q_mask is not
+// read for it. This is the only place that decides it.
+struct QMask {
+  const int32_t* q_mask;
+  int64_t stride;
+  int n_masks;
+  int nq;  // queries of the pass
+};
+// the query's mask number, or -1: unfiltered
+__device__ __forceinline__ int32_t qmask_index(const QMask& qm, int q) {
+  const int32_t m = q >= 0 && q < qm.nq ? qm.q_mask[q] : -1;
+  return m >= 0 && m < qm.n_masks ? m : -1;
+}
+// the query's row of the stack, or null: unfiltered
+__device__ __forceinline__ const uint64_t* qmask_row(const uint64_t* __restrict__ row_masks,
+                                                      const QMask& qm, int q) {
+  const int32_t m = qmask_index(qm, q);
+  return m >= 0 ? row_masks + (size_t)m * qm.stride : nullptr;
+}
 }  // namespace armi

@@ -39,6 +39,8 @@ namespace {
 using armi::TILE_ROWS;
 using armi::kNegInfD;
 using armi::kNoOrd;
+using armi::QMask;  // one row mask per query (armi_index.h)
+using armi::qmask_row;
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -2242,8 +2244,7 @@ __device__ __forceinline__ void collect_merge_body(
     const uint64_t* __restrict__ row_mask, int64_t n_rows, const uint16_t* __restrict__ queries,
     const double* __restrict__ inv_q, int k, int64_t ordinal_base, float* __restrict__ out_scores,
     int64_t* __restrict__ out_ids, double* __restrict__ out_rank, int32_t* __restrict__ out_count,
-    uint32_t* __restrict__ flags, const int32_t* __restrict__ q_mask = nullptr, int n_masks = 0,
-    int64_t mask_stride = 0, uint32_t flag_or = 0u){
+    uint32_t* __restrict__ flags, const QMask qm = QMask{}, uint32_t flag_or = 0u){
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   double* key = reinterpret_cast<double*>(smem);                            // [2 * kColChunk]
   int64_t* ord = reinterpret_cast<int64_t*>(smem + 2 * kColChunk * 8);       // [2 * kColChunk]
@@ -2255,13 +2256,9 @@ __device__ __forceinline__ void collect_merge_body(
                       out_count);
     if (tid == 0) flags[qg] = ARMI_FLAG_FALLBACK | flag_or;
   };
-  // q_mask (armi_dense_topk_qmask): row_mask is the call's [n_masks][mask_stride] masks and the
-  // helpers filter by the query's own (none for -1 and for an entry outside [0, n_masks))
-  auto mask_of = [&](int qg) -> const uint64_t* {
-    if (!q_mask) return row_mask;
-    const int m = q_mask[qg];
-    return m >= 0 && m < n_masks ? row_mask + (int64_t)m * mask_stride : nullptr;
-  };
+  // qm.q_mask (armi_dense_topk_qmask): row_mask is the call's stack of masks and the helpers
+  // filter by the query's own row of it (qmask_row)
+  auto mask_of = [&](int qg) { return qm.q_mask ? qmask_row(row_mask, qm, qg) : row_mask; };
   if (bid < nq) {  // the query's own workgroup
     const int qg = bid;
     if (flags[qg] & ARMI_FLAG_CERTIFIED) {  // workgroup-uniform
@@ -2325,7 +2322,9 @@ __global__ __launch_bounds__(kDenseMergeThreads) void dense_collect_merge_kernel
 }
 
 // The same for armi_dense_topk_qmask: the helpers of an overflowed query filter by that query's
-// own mask, and every query's flag word gets flag_or (ARMI_FLAG_QMASK).
+// own mask, and every query's flag word gets flag_or (ARMI_FLAG_QMASK). (Like the other kernels
+// with a query count of their own, it takes the mask arguments loose and builds the QMask over
+// that count: the body's queries are then inside it by construction.)
 template <int DIM>
 __global__ __launch_bounds__(kDenseMergeThreads) void dense_collect_merge_qmask_kernel(
     const int32_t* __restrict__ col_cnt, int32_t* __restrict__ col_list, int col_cap,
@@ -2339,7 +2338,7 @@ __global__ __launch_bounds__(kDenseMergeThreads) void dense_collect_merge_qmask_
     uint32_t flag_or) {
   collect_merge_body<DIM>(blockIdx.x, (int)gridDim.x - nq, col_cnt, col_list, col_cap, help_done, nq, rows,
       inv_norm, norm2, row_masks, n_rows, queries, inv_q, k, ordinal_base, out_scores, out_ids,
-      out_rank, out_count, flags, q_mask, n_masks, mask_stride, flag_or);
+      out_rank, out_count, flags, QMask{q_mask, mask_stride, n_masks, nq}, flag_or);
 }
 
 // First kernel of armi_dense_topk_qmask: the call's mask image [n_qb][T][kQB] of u32 (see
@@ -2351,14 +2350,15 @@ __global__ __launch_bounds__(kDenseMergeThreads) void dense_collect_merge_qmask_
 // words then turn through LDS so that each tile's 16 words leave as one 64-B run. (One workgroup
 // per 64 queries left 49 workgroups at 100k rows, each thread walking 16 x 32 loads: 0.16 ms at
 // 100k and at 1M rows alike, latency, not bytes.)
-// Bits of ordinals >= n_rows and words of queries past nq are 0; a query without a mask (-1, or an
-// entry outside [0, n_masks), which never indexes row_masks) gets every row below n_rows.
+// Bits of ordinals >= n_rows and words of queries past nq are 0; a query without a mask
+// (qmask_row: null) gets every row below n_rows.
 constexpr int kPrepTiles = 64;
 constexpr int kPrepQueries = 16;
 static_assert(kQB % kPrepQueries == 0 && kPrepQueries % 4 == 0, "query groups of the prep grid");
 __global__ __launch_bounds__(256) void qmask_prep_kernel(
     const uint64_t* __restrict__ row_masks, int64_t mask_stride, const int32_t* __restrict__ q_mask,
     int n_masks, int nq, int64_t n_rows, int64_t T, int64_t perm_mul, uint32_t* __restrict__ out) {
+  const QMask qm{q_mask, mask_stride, n_masks, nq};
   __shared__ uint32_t words[kPrepTiles][kPrepQueries + 1];  // [residue][query], padded
   const int lane = threadIdx.x & 63;
   const int wave = armi::wave_id();
@@ -2371,8 +2371,7 @@ __global__ __launch_bounds__(256) void qmask_prep_kernel(
     const int q = qb * kQB + c0 + c;
     uint32_t w = 0;
     if (q < nq && u < T) {
-      const int m = q_mask[q];  // (wave-uniform)
-      const uint64_t* mk = m >= 0 && m < n_masks ? row_masks + (int64_t)m * mask_stride : nullptr;
+      const uint64_t* mk = qmask_row(row_masks, qm, q);  // (wave-uniform)
 #pragma unroll
       for (int p = 0; p < TILE_ROWS; ++p) {
         const int64_t i = u + p * T;
@@ -2796,29 +2795,120 @@ int launch_exact(const armi_index* idx, const uint16_t* queries, int nq, int k,
   return ARMI_OK;
 }
 
+// The row filter of one dense call. qm.q_mask == nullptr (armi_dense_topk): mask is the call's one
+// row mask or null, and img the room for its image in int8 order (Workspace::mask_img, u64 words).
+// qm.q_mask set (armi_dense_topk_qmask): mask is the [n_masks][stride] stack, qm names each query's
+// row of it and img is the room for the call's mask image (qmask_prep_kernel, u32 words); every
+// stage that tests a mask then runs its per-query sibling.
+struct DenseFilter {
+  const uint64_t* mask;
+  QMask qm;
+  void* img;
+};
+
+// Second pass for the uncertified queries (both kernels exit at once when every query of the
+// call is certified): int8 collect over the whole shard, then exact rescore of the lists. img:
+// the mask image the first pass read (null: no filter).
 template <int DIM>
 int dense_second_pass(const armi_index* idx, const uint16_t* queries, int nq, int k,
-                      const uint64_t* row_mask, const uint64_t* mask_i8, float* out_scores,
-                      int64_t* out_ids, double* out_rank, int32_t* out_count, uint32_t* out_flags,
-                      const Workspace& w, hipStream_t stream);
+                      const DenseFilter& f, const void* img, float* out_scores, int64_t* out_ids,
+                      double* out_rank, int32_t* out_count, uint32_t* out_flags,
+                      const Workspace& w, hipStream_t stream) {
+  const bool qmask = f.qm.q_mask != nullptr;
+  // no int8 image to collect from (never a per-query-mask call, qmask_supported): the exact scan,
+  // flagged queries only
+  if (idx->rows8 == nullptr)
+    return launch_exact<DIM>(idx, queries, nq, k, f.mask, out_scores, out_ids, out_rank, out_count,
+                             out_flags, 1, w, stream);
+  {
+    const ScanPlan cp = plan_scan(idx, k, 1);  // one block's ranges; blocks of one range share an XCD
+    const int n_qb = (nq + kQB - 1) / kQB;
+    const dim3 grid(scan_grid(n_qb, cp.n_wg));
+    const bool nt = use_nt_stream(idx);
+    if (qmask) {
+      auto kern = nt ? dense_scan_i8_qmask_kernel<DIM, true, true>
+                     : dense_scan_i8_qmask_kernel<DIM, true, false>;
+      if (int rc = allow_lds(kern, scan_i8_lds_bytes<DIM>())) return rc;
+      kern<<<grid, dim3(kThreads), scan_i8_lds_bytes<DIM>(), stream>>>(
+          idx->rows8, idx->a32, idx->e32, static_cast<const uint32_t*>(img), idx->n_rows,
+          idx->n_tiles, cp.tiles_per_wg, cp.n_wg, n_qb, queries, nq, nullptr, nullptr, nullptr,
+          idx->tile_ord, out_flags, w.thr, w.col_cnt, w.col_list, kCollectCap);
+      ARMI_LAUNCHED("dense_scan_i8_qmask_kernel(collect)");
+    } else {
+      auto kern = nt ? dense_scan_i8_kernel<DIM, true, true> : dense_scan_i8_kernel<DIM, true, false>;
+      if (int rc = allow_lds(kern, scan_i8_lds_bytes<DIM>())) return rc;
+      kern<<<grid, dim3(kThreads), scan_i8_lds_bytes<DIM>(), stream>>>(
+          idx->rows8, idx->a32, idx->e32, static_cast<const uint64_t*>(img), idx->n_rows,
+          idx->n_tiles, cp.tiles_per_wg, cp.n_wg, n_qb, queries, nq, nullptr, nullptr, nullptr,
+          idx->tile_ord, out_flags, w.thr, w.col_cnt, w.col_list, kCollectCap, 1);
+      ARMI_LAUNCHED("dense_scan_i8_kernel(collect)");
+    }
+  }
+  // helpers for overflowed lists: each writes k rows into the list, so n_help * k <= the cap
+  const int n_help = std::max(1, std::min<int>(kMaxHelp, kCollectCap / k));
+  const dim3 grid(nq + n_help);
+  if (qmask) {
+    if (int rc = allow_lds(dense_collect_merge_qmask_kernel<DIM>, kColMergeLds)) return rc;
+    dense_collect_merge_qmask_kernel<DIM><<<grid, dim3(kDenseMergeThreads), kColMergeLds, stream>>>(
+        w.col_cnt, w.col_list, kCollectCap, w.help_done, nq, idx->rows, idx->inv_norm, idx->norm2,
+        f.mask, f.qm.stride, f.qm.q_mask, f.qm.n_masks, idx->n_rows, queries, w.inv_q, k,
+        idx->ordinal_base, out_scores, out_ids, out_rank, out_count, out_flags, ARMI_FLAG_QMASK);
+    ARMI_LAUNCHED("dense_collect_merge_qmask_kernel");
+  } else {
+    if (int rc = allow_lds(dense_collect_merge_kernel<DIM>, kColMergeLds)) return rc;
+    dense_collect_merge_kernel<DIM><<<grid, dim3(kDenseMergeThreads), kColMergeLds, stream>>>(
+        w.col_cnt, w.col_list, kCollectCap, w.help_done, nq, idx->rows, idx->inv_norm, idx->norm2,
+        f.mask, idx->n_rows, queries, w.inv_q, k, idx->ordinal_base, out_scores, out_ids,
+        out_rank, out_count, out_flags);
+    ARMI_LAUNCHED("dense_collect_merge_kernel");
+  }
+  return ARMI_OK;
+}
 
+// armi_dense_topk_qmask answers armi_dense_topk's int8-filter call shape (1-2 query blocks) only;
+// its mask image sits in front of the armi_dense_topk workspace.
+bool qmask_supported(const armi_index* idx, int nq, int k) {
+  return idx->rows8 != nullptr && nq >= 1 && nq <= 2 * kQB && k >= 1 && k <= kI8MaxK;
+}
+
+size_t qmask_img_bytes(const armi_index* idx, int nq) {
+  const size_t n_qb = (size_t)(nq + kQB - 1) / kQB;
+  return armi::align_up(n_qb * (size_t)std::max<int64_t>(idx->n_tiles, 1) * kQB * 4, 256);
+}
+
+// The launch sequence of armi_dense_topk and armi_dense_topk_qmask (arguments checked by the entry
+// points): the mask image, the first pass, the merge, the second pass. A per-query-mask call
+// (qmask_supported) takes the int8-filter first pass, the merge unchanged (its candidates are
+// enabled rows) and the int8 collect pass.
 template <int DIM>
 int dense_topk_impl(const armi_index* idx, const uint16_t* queries, int nq, int k,
-                    const uint64_t* row_mask, float* out_scores, int64_t* out_ids,
-                    double* out_rank, int32_t* out_count, uint32_t* out_flags,
-                    const Workspace& w, hipStream_t stream) {
+                    const DenseFilter& f, float* out_scores, int64_t* out_ids, double* out_rank,
+                    int32_t* out_count, uint32_t* out_flags, const Workspace& w,
+                    hipStream_t stream) {
+  const bool qmask = f.qm.q_mask != nullptr;
   const ScanPlan sp = plan_scan(idx, k, nq);
   int n_wg = sp.n_wg;
   int kc = sp.kc;
   const int64_t T = std::max<int64_t>(idx->n_tiles, 1);
   // the int8 passes (first pass and collect pass) read the filter in image order
-  const uint64_t* mask_i8 = nullptr;
-  if (row_mask && idx->rows8 != nullptr) {
+  const void* img = nullptr;
+  if (qmask) {
+    const int rc_l = armi::timed_kernel(
+        ARMI_TIMING_QMASK_PREP, qmask_prep_kernel,
+        dim3((unsigned)((T + kPrepTiles - 1) / kPrepTiles), sp.n_qb * (kQB / kPrepQueries)),
+        dim3(256), 0, stream, f.mask, f.qm.stride, f.qm.q_mask, f.qm.n_masks, nq, idx->n_rows, T,
+        idx->perm_mul, static_cast<uint32_t*>(f.img));
+    ARMI_LAUNCHED("qmask_prep_kernel");
+    if (rc_l) return rc_l;
+    img = f.img;
+  } else if (f.mask && idx->rows8 != nullptr) {
     scan_prep_kernel<<<dim3((unsigned)std::max<int64_t>(1, (T * 32 + 255) / 256)), dim3(256), 0,
-                       stream>>>(row_mask, idx->n_rows, T, idx->tile_ord, w.mask_img);
+                       stream>>>(f.mask, idx->n_rows, T, idx->tile_ord,
+                                 static_cast<uint64_t*>(f.img));
     ARMI_LAUNCHED("scan_prep_kernel");
-    mask_i8 = w.mask_img;
+    img = f.img;
   }
+  const uint64_t* mask_i8 = static_cast<const uint64_t*>(img);  // (the shared-mask forms)
   if (use_gemm_scan(nq)) {
     const bool i8 = use_tiled_i8(idx, k);
     const int64_t n_scan = gemm_rows(idx, k);
@@ -2841,7 +2931,7 @@ int dense_topk_impl(const armi_index* idx, const uint16_t* queries, int nq, int 
     if (int rc = allow_lds(kern, gemm_w4_lds_bytes<DIM>())) return rc;
     const int rc_l = armi::timed_kernel(
         ARMI_TIMING_DENSE_SCAN, kern, dim3(gp.grid), dim3(kW4Threads), gemm_w4_lds_bytes<DIM>(),
-        stream, idx->rows, idx->inv_norm32, i8 ? mask_i8 : row_mask, n_scan, gp.rows_per_range,
+        stream, idx->rows, idx->inv_norm32, i8 ? mask_i8 : f.mask, n_scan, gp.rows_per_range,
         gp.n_ranges, gp.n_qb, queries, nq, w.cand_key, w.cand_row, w.cand_bound,
         (const int8_t*)idx->rows8, (const float*)idx->a32, (const float*)idx->e32,
         (const int32_t*)idx->tile_ord, (const int8_t*)w.q8, (const float4*)w.qsc);
@@ -2849,24 +2939,39 @@ int dense_topk_impl(const armi_index* idx, const uint16_t* queries, int nq, int 
     if (rc_l) return rc_l;
   } else if (use_i8_filter(idx, k)) {
     kc = kc_i8(k);
-    auto kern = use_nt_stream(idx) ? dense_scan_i8_kernel<DIM, false, true>
-                                   : dense_scan_i8_kernel<DIM, false, false>;
-    if (int rc = allow_lds(kern, scan_i8_lds_bytes<DIM>())) return rc;
-    const int rc_l = armi::timed_kernel(
-        ARMI_TIMING_DENSE_SCAN, kern, dim3(sp.grid), dim3(kThreads), scan_i8_lds_bytes<DIM>(),
-        stream, (const int8_t*)idx->rows8, (const float*)idx->a32, (const float*)idx->e32,
-        mask_i8, idx->n_rows, idx->n_tiles, sp.tiles_per_wg, sp.n_wg, sp.n_qb, queries, nq,
-        w.cand_key, w.cand_row, w.cand_bound, (const int32_t*)idx->tile_ord,
-        (const uint32_t*)nullptr, (const float*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, 0,
-        sp.xcd_step);
-    ARMI_LAUNCHED("dense_scan_i8_kernel");
-    if (rc_l) return rc_l;
+    const bool nt = use_nt_stream(idx);
+    if (qmask) {  // (no xcd_step: the grid is the plain one)
+      auto kern = nt ? dense_scan_i8_qmask_kernel<DIM, false, true>
+                     : dense_scan_i8_qmask_kernel<DIM, false, false>;
+      if (int rc = allow_lds(kern, scan_i8_lds_bytes<DIM>())) return rc;
+      const int rc_l = armi::timed_kernel(
+          ARMI_TIMING_DENSE_SCAN, kern, dim3(scan_grid(sp.n_qb, sp.n_wg)), dim3(kThreads),
+          scan_i8_lds_bytes<DIM>(), stream, (const int8_t*)idx->rows8, (const float*)idx->a32,
+          (const float*)idx->e32, static_cast<const uint32_t*>(img), idx->n_rows, idx->n_tiles,
+          sp.tiles_per_wg, sp.n_wg, sp.n_qb, queries, nq, w.cand_key, w.cand_row, w.cand_bound,
+          (const int32_t*)idx->tile_ord, (const uint32_t*)nullptr, (const float*)nullptr,
+          (int32_t*)nullptr, (int32_t*)nullptr, 0);
+      ARMI_LAUNCHED("dense_scan_i8_qmask_kernel");
+      if (rc_l) return rc_l;
+    } else {
+      auto kern = nt ? dense_scan_i8_kernel<DIM, false, true> : dense_scan_i8_kernel<DIM, false, false>;
+      if (int rc = allow_lds(kern, scan_i8_lds_bytes<DIM>())) return rc;
+      const int rc_l = armi::timed_kernel(
+          ARMI_TIMING_DENSE_SCAN, kern, dim3(sp.grid), dim3(kThreads), scan_i8_lds_bytes<DIM>(),
+          stream, (const int8_t*)idx->rows8, (const float*)idx->a32, (const float*)idx->e32,
+          mask_i8, idx->n_rows, idx->n_tiles, sp.tiles_per_wg, sp.n_wg, sp.n_qb, queries, nq,
+          w.cand_key, w.cand_row, w.cand_bound, (const int32_t*)idx->tile_ord,
+          (const uint32_t*)nullptr, (const float*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, 0,
+          sp.xcd_step);
+      ARMI_LAUNCHED("dense_scan_i8_kernel");
+      if (rc_l) return rc_l;
+    }
   } else {
     if (int rc = allow_lds(dense_scan_kernel<DIM>, scan_lds_bytes<DIM>())) return rc;
     const int rc_l = armi::timed_kernel(
         ARMI_TIMING_DENSE_SCAN, dense_scan_kernel<DIM>, dim3(sp.grid), dim3(kThreads),
         scan_lds_bytes<DIM>(), stream, (const uint16_t*)idx->rows, (const float*)idx->inv_norm32,
-        row_mask, idx->n_rows, idx->n_tiles, sp.tiles_per_wg, sp.n_wg, sp.n_qb, queries, nq,
+        f.mask, idx->n_rows, idx->n_tiles, sp.tiles_per_wg, sp.n_wg, sp.n_qb, queries, nq,
         w.cand_key, w.cand_row, w.cand_bound);
     ARMI_LAUNCHED("dense_scan_kernel");
     if (rc_l) return rc_l;
@@ -2884,120 +2989,8 @@ int dense_topk_impl(const armi_index* idx, const uint16_t* queries, int nq, int 
       idx->ordinal_base, out_scores, out_ids, out_rank, out_count, out_flags, w.thr, w.col_cnt,
       w.help_done, merge_two_stage(kc) ? 1 : 0);
   ARMI_LAUNCHED("dense_merge_kernel");
-  return dense_second_pass<DIM>(idx, queries, nq, k, row_mask, mask_i8, out_scores, out_ids,
-                                out_rank, out_count, out_flags, w, stream);
-}
-
-// Second pass for the uncertified queries (both kernels exit at once when every query of the
-// call is certified): int8 collect over the whole shard, then exact rescore of the lists.
-template <int DIM>
-int dense_second_pass(const armi_index* idx, const uint16_t* queries, int nq, int k,
-                      const uint64_t* row_mask, const uint64_t* mask_i8, float* out_scores,
-                      int64_t* out_ids, double* out_rank, int32_t* out_count, uint32_t* out_flags,
-                      const Workspace& w, hipStream_t stream) {
-  if (idx->rows8 == nullptr)  // no int8 image to collect from: the exact scan, flagged queries only
-    return launch_exact<DIM>(idx, queries, nq, k, row_mask, out_scores, out_ids, out_rank, out_count,
-                             out_flags, 1, w, stream);
-  {
-    const ScanPlan cp = plan_scan(idx, k, 1);  // one block's ranges; blocks of one range share an XCD
-    const int n_qb = (nq + kQB - 1) / kQB;
-    const int grid = scan_grid(n_qb, cp.n_wg);
-    auto kern = use_nt_stream(idx) ? dense_scan_i8_kernel<DIM, true, true>
-                                   : dense_scan_i8_kernel<DIM, true, false>;
-    if (int rc = allow_lds(kern, scan_i8_lds_bytes<DIM>())) return rc;
-    kern<<<dim3(grid), dim3(kThreads), scan_i8_lds_bytes<DIM>(), stream>>>(
-        idx->rows8, idx->a32, idx->e32, mask_i8, idx->n_rows, idx->n_tiles, cp.tiles_per_wg,
-        cp.n_wg, n_qb, queries, nq, nullptr, nullptr, nullptr, idx->tile_ord,
-        out_flags, w.thr, w.col_cnt, w.col_list, kCollectCap, 1);
-    ARMI_LAUNCHED("dense_scan_i8_kernel(collect)");
-  }
-  if (int rc = allow_lds(dense_collect_merge_kernel<DIM>, kColMergeLds)) return rc;
-  // helpers for overflowed lists: each writes k rows into the list, so n_help * k <= the cap
-  const int n_help = std::max(1, std::min<int>(kMaxHelp, kCollectCap / k));
-  dense_collect_merge_kernel<DIM><<<dim3(nq + n_help), dim3(kDenseMergeThreads), kColMergeLds,
-                                    stream>>>(
-      w.col_cnt, w.col_list, kCollectCap, w.help_done, nq, idx->rows, idx->inv_norm, idx->norm2,
-      row_mask, idx->n_rows, queries, w.inv_q, k, idx->ordinal_base, out_scores, out_ids,
-      out_rank, out_count, out_flags);
-  ARMI_LAUNCHED("dense_collect_merge_kernel");
-  return ARMI_OK;
-}
-
-// armi_dense_topk_qmask: armi_dense_topk's int8-filter call (1-2 query blocks) with one row mask
-// per query. Five launches: the mask image, the int8 first pass, the merge (unchanged: its
-// candidates are enabled rows), the collect pass and its merge. Calls of this shape only
-// (qmask_supported); the mask image sits in front of the armi_dense_topk workspace.
-bool qmask_supported(const armi_index* idx, int nq, int k) {
-  return idx->rows8 != nullptr && nq >= 1 && nq <= 2 * kQB && k >= 1 && k <= kI8MaxK;
-}
-
-size_t qmask_img_bytes(const armi_index* idx, int nq) {
-  const size_t n_qb = (size_t)(nq + kQB - 1) / kQB;
-  return armi::align_up(n_qb * (size_t)std::max<int64_t>(idx->n_tiles, 1) * kQB * 4, 256);
-}
-
-template <int DIM>
-int dense_topk_qmask_impl(const armi_index* idx, const uint16_t* queries, int nq, int k,
-                          const uint64_t* row_masks, int64_t mask_stride, const int32_t* q_mask,
-                          int n_masks, uint32_t* mask_img, float* out_scores, int64_t* out_ids,
-                          double* out_rank, int32_t* out_count, uint32_t* out_flags,
-                          const Workspace& w, hipStream_t stream) {
-  const ScanPlan sp = plan_scan(idx, k, nq);
-  const int64_t T = std::max<int64_t>(idx->n_tiles, 1);
-  const bool nt = use_nt_stream(idx);
-  {
-    const int rc_l = armi::timed_kernel(
-        ARMI_TIMING_QMASK_PREP, qmask_prep_kernel,
-        dim3((unsigned)((T + kPrepTiles - 1) / kPrepTiles), sp.n_qb * (kQB / kPrepQueries)),
-        dim3(256), 0, stream,
-        row_masks, mask_stride, q_mask, n_masks, nq, idx->n_rows, T, idx->perm_mul, mask_img);
-    ARMI_LAUNCHED("qmask_prep_kernel");
-    if (rc_l) return rc_l;
-  }
-  {
-    auto kern = nt ? dense_scan_i8_qmask_kernel<DIM, false, true>
-                   : dense_scan_i8_qmask_kernel<DIM, false, false>;
-    if (int rc = allow_lds(kern, scan_i8_lds_bytes<DIM>())) return rc;
-    const int rc_l = armi::timed_kernel(
-        ARMI_TIMING_DENSE_SCAN, kern, dim3(scan_grid(sp.n_qb, sp.n_wg)), dim3(kThreads),
-        scan_i8_lds_bytes<DIM>(), stream, (const int8_t*)idx->rows8, (const float*)idx->a32,
-        (const float*)idx->e32, (const uint32_t*)mask_img, idx->n_rows, idx->n_tiles,
-        sp.tiles_per_wg, sp.n_wg, sp.n_qb, queries, nq, w.cand_key, w.cand_row, w.cand_bound,
-        (const int32_t*)idx->tile_ord, (const uint32_t*)nullptr, (const float*)nullptr,
-        (int32_t*)nullptr, (int32_t*)nullptr, 0);
-    ARMI_LAUNCHED("dense_scan_i8_qmask_kernel");
-    if (rc_l) return rc_l;
-  }
-  const int kc = kc_i8(k);
-  ARMI_REQUIRE(sp.n_wg >= 1 && sp.n_wg * kKW <= kMaxPool,
-               "dense merge: the candidate pool must fit one filter round (<= 256 lists)");
-  int sel_col = 1, sel_rank = kc;
-  merge_select(kc, sp.n_wg, sel_col, sel_rank);
-  dense_merge_kernel<DIM><<<dim3(nq), dim3(kDenseMergeThreads), kMergeLds, stream>>>(
-      w.cand_key, w.cand_row, w.cand_bound, sp.n_wg, nq, idx->rows, idx->inv_norm, queries,
-      w.inv_q, w.qnorm, k, kc, sel_col, sel_rank, idx->ordinal_base, out_scores, out_ids, out_rank,
-      out_count, out_flags, w.thr, w.col_cnt, w.help_done, merge_two_stage(kc) ? 1 : 0);
-  ARMI_LAUNCHED("dense_merge_kernel");
-  {
-    const ScanPlan cp = plan_scan(idx, k, 1);
-    auto kern = nt ? dense_scan_i8_qmask_kernel<DIM, true, true>
-                   : dense_scan_i8_qmask_kernel<DIM, true, false>;
-    if (int rc = allow_lds(kern, scan_i8_lds_bytes<DIM>())) return rc;
-    kern<<<dim3(scan_grid(sp.n_qb, cp.n_wg)), dim3(kThreads), scan_i8_lds_bytes<DIM>(), stream>>>(
-        idx->rows8, idx->a32, idx->e32, mask_img, idx->n_rows, idx->n_tiles, cp.tiles_per_wg,
-        cp.n_wg, sp.n_qb, queries, nq, nullptr, nullptr, nullptr, idx->tile_ord, out_flags, w.thr,
-        w.col_cnt, w.col_list, kCollectCap);
-    ARMI_LAUNCHED("dense_scan_i8_qmask_kernel(collect)");
-  }
-  if (int rc = allow_lds(dense_collect_merge_qmask_kernel<DIM>, kColMergeLds)) return rc;
-  const int n_help = std::max(1, std::min<int>(kMaxHelp, kCollectCap / k));
-  dense_collect_merge_qmask_kernel<DIM><<<dim3(nq + n_help), dim3(kDenseMergeThreads),
-                                          kColMergeLds, stream>>>(
-      w.col_cnt, w.col_list, kCollectCap, w.help_done, nq, idx->rows, idx->inv_norm, idx->norm2,
-      row_masks, mask_stride, q_mask, n_masks, idx->n_rows, queries, w.inv_q, k,
-      idx->ordinal_base, out_scores, out_ids, out_rank, out_count, out_flags, ARMI_FLAG_QMASK);
-  ARMI_LAUNCHED("dense_collect_merge_qmask_kernel");
-  return ARMI_OK;
+  return dense_second_pass<DIM>(idx, queries, nq, k, f, img, out_scores, out_ids, out_rank,
+                                out_count, out_flags, w, stream);
 }
 
 
@@ -3027,15 +3020,13 @@ constexpr int tail_scan_lds_bytes() { return scan_img_bytes<DIM>() + kQB * 8 + k
 // the caller's masks. The tail is scanned in ordinal order, so the 32 rows of tile t are the 32-bit
 // word t of a mask row (uint64 word t / 2, its low half first); t < n_tiles <= 2 ceil(rows / 64)
 // <= 2 mask_stride, so the read stays inside the query's row of the stack. A lane keeps the mask
-// rows of its two queries (null: unfiltered: -1, an entry outside [0, n_masks), a query past the
-// batch, for which q_mask is not read), loads their words of a tile with the tile and tests the
-// row's bit together with >= thr. row_scales runs without a mask; bits of padding and invalid rows
-// do nothing, their scale is NaN.
+// rows of its two queries (qmask_row; null: unfiltered, as a query past the batch is), loads their
+// words of a tile with the tile and tests the row's bit together with >= thr. row_scales runs
+// without a mask; bits of padding and invalid rows do nothing, their scale is NaN.
 template <int DIM, bool QMASK>
 __device__ __forceinline__ void dense_tail_scan_body(
     const uint16_t* __restrict__ rows, const float* __restrict__ inv_norm32,
-    const uint64_t* __restrict__ row_mask, const int32_t* __restrict__ q_mask, int n_masks,
-    int64_t mask_stride, int64_t n_rows, int64_t n_tiles,
+    const uint64_t* __restrict__ row_mask, const QMask qm, int64_t n_rows, int64_t n_tiles,
     const uint16_t* __restrict__ queries_all, int nq_all, int k,
     const double* __restrict__ main_rank, const int32_t* __restrict__ main_count,
     int32_t* __restrict__ wg_cnt, int32_t* __restrict__ wg_list) {
@@ -3108,15 +3099,9 @@ __device__ __forceinline__ void dense_tail_scan_body(
   const uint32_t* mrow0 = nullptr;
   const uint32_t* mrow1 = nullptr;
   if constexpr (QMASK) {
-    auto mask_words = [&](int ql) -> const uint32_t* {
-      if (ql >= nq) return nullptr;
-      const int32_t m = q_mask[q0 + ql];
-      return m >= 0 && m < n_masks
-                 ? reinterpret_cast<const uint32_t*>(row_mask + (int64_t)m * mask_stride)
-                 : nullptr;
-    };
-    mrow0 = mask_words(r);
-    mrow1 = mask_words(32 + r);
+    const QMask qb{qm.q_mask + q0, qm.stride, qm.n_masks, nq};  // the block's queries
+    mrow0 = reinterpret_cast<const uint32_t*>(qmask_row(row_mask, qb, r));
+    mrow1 = reinterpret_cast<const uint32_t*>(qmask_row(row_mask, qb, 32 + r));
   }
 
   for (; t < t_end; t += kWaves) {
@@ -3173,7 +3158,7 @@ __global__ __launch_bounds__(kThreads) void dense_tail_scan_kernel(
     const uint16_t* __restrict__ queries_all, int nq_all, int k,
     const double* __restrict__ main_rank, const int32_t* __restrict__ main_count,
     int32_t* __restrict__ wg_cnt, int32_t* __restrict__ wg_list) {
-  dense_tail_scan_body<DIM, false>(rows, inv_norm32, row_mask, nullptr, 0, 0, n_rows, n_tiles,
+  dense_tail_scan_body<DIM, false>(rows, inv_norm32, row_mask, QMask{}, n_rows, n_tiles,
                                    queries_all, nq_all, k, main_rank, main_count, wg_cnt, wg_list);
 }
 
@@ -3186,9 +3171,9 @@ __global__ __launch_bounds__(kThreads) void dense_tail_scan_qmask_kernel(
     const uint16_t* __restrict__ queries_all, int nq_all, int k,
     const double* __restrict__ main_rank, const int32_t* __restrict__ main_count,
     int32_t* __restrict__ wg_cnt, int32_t* __restrict__ wg_list) {
-  dense_tail_scan_body<DIM, true>(rows, inv_norm32, row_masks, q_mask, n_masks, mask_stride, n_rows,
-                                  n_tiles, queries_all, nq_all, k, main_rank, main_count, wg_cnt,
-                                  wg_list);
+  dense_tail_scan_body<DIM, true>(rows, inv_norm32, row_masks,
+                                  QMask{q_mask, mask_stride, n_masks, nq_all}, n_rows, n_tiles,
+                                  queries_all, nq_all, k, main_rank, main_count, wg_cnt, wg_list);
 }
 
 // LDS of dense_tail_finish_kernel: collect_top_rows' sort arrays, the gathered survivor rows, one
@@ -3203,9 +3188,8 @@ template <int DIM, bool QMASK>
 __device__ __forceinline__ void dense_tail_finish_body(
     const int32_t* __restrict__ wg_cnt, const int32_t* __restrict__ wg_list, int n_wg,
     const uint16_t* __restrict__ rows, const double* __restrict__ inv_norm,
-    const int64_t* __restrict__ norm2, const uint64_t* __restrict__ row_mask,
-    const int32_t* __restrict__ q_mask, int n_masks, int64_t mask_stride, int64_t n_rows,
-    const uint16_t* __restrict__ queries, int k, int64_t ordinal_base,
+    const int64_t* __restrict__ norm2, const uint64_t* __restrict__ row_mask, const QMask qm,
+    int64_t n_rows, const uint16_t* __restrict__ queries, int k, int64_t ordinal_base,
     const int64_t* __restrict__ main_ids, const double* __restrict__ main_rank,
     const int32_t* __restrict__ main_count, float* __restrict__ out_scores,
     int64_t* __restrict__ out_ids, double* __restrict__ out_rank, int32_t* __restrict__ out_count,
@@ -3279,11 +3263,7 @@ __device__ __forceinline__ void dense_tail_finish_body(
     // More than kTailCap survivors means more than kTailCap rows, so the rows take the chunked
     // path of collect_top_rows, which leaves the best kColChunk of them in front.
     static_assert(kTailCap >= kColChunk, "an overflowed tail is longer than one collect chunk");
-    const uint64_t* mrow = row_mask;
-    if constexpr (QMASK) {
-      const int32_t m = q_mask[qg];
-      mrow = m >= 0 && m < n_masks ? row_mask + (int64_t)m * mask_stride : nullptr;
-    }
+    const uint64_t* mrow = QMASK ? qmask_row(row_mask, qm, qg) : row_mask;
     collect_top_rows<DIM>(nullptr, 0, n_rows, k, qf, rows, inv_norm, norm2, mrow, ordinal_base,
                           key, ord);
     p = kColChunk;
@@ -3314,8 +3294,8 @@ __global__ __launch_bounds__(kDenseMergeThreads) void dense_tail_finish_kernel(
     const int32_t* __restrict__ main_count, float* __restrict__ out_scores,
     int64_t* __restrict__ out_ids, double* __restrict__ out_rank, int32_t* __restrict__ out_count,
     uint32_t* __restrict__ out_flags) {
-  dense_tail_finish_body<DIM, false>(wg_cnt, wg_list, n_wg, rows, inv_norm, norm2, row_mask, nullptr,
-                                     0, 0, n_rows, queries, k, ordinal_base, main_ids, main_rank,
+  dense_tail_finish_body<DIM, false>(wg_cnt, wg_list, n_wg, rows, inv_norm, norm2, row_mask, QMask{},
+                                     n_rows, queries, k, ordinal_base, main_ids, main_rank,
                                      main_count, out_scores, out_ids, out_rank, out_count,
                                      out_flags);
 }
@@ -3325,16 +3305,15 @@ template <int DIM>
 __global__ __launch_bounds__(kDenseMergeThreads) void dense_tail_finish_qmask_kernel(
     const int32_t* __restrict__ wg_cnt, const int32_t* __restrict__ wg_list, int n_wg,
     const uint16_t* __restrict__ rows, const double* __restrict__ inv_norm,
-    const int64_t* __restrict__ norm2, const uint64_t* __restrict__ row_masks,
-    const int32_t* __restrict__ q_mask, int n_masks, int64_t mask_stride, int64_t n_rows,
-    const uint16_t* __restrict__ queries, int k, int64_t ordinal_base,
+    const int64_t* __restrict__ norm2, const uint64_t* __restrict__ row_masks, const QMask qm,
+    int64_t n_rows, const uint16_t* __restrict__ queries, int k, int64_t ordinal_base,
     const int64_t* __restrict__ main_ids, const double* __restrict__ main_rank,
     const int32_t* __restrict__ main_count, float* __restrict__ out_scores,
     int64_t* __restrict__ out_ids, double* __restrict__ out_rank, int32_t* __restrict__ out_count,
     uint32_t* __restrict__ out_flags) {
-  dense_tail_finish_body<DIM, true>(wg_cnt, wg_list, n_wg, rows, inv_norm, norm2, row_masks, q_mask,
-                                    n_masks, mask_stride, n_rows, queries, k, ordinal_base, main_ids,
-                                    main_rank, main_count, out_scores, out_ids, out_rank, out_count,
+  dense_tail_finish_body<DIM, true>(wg_cnt, wg_list, n_wg, rows, inv_norm, norm2, row_masks, qm,
+                                    n_rows, queries, k, ordinal_base, main_ids, main_rank,
+                                    main_count, out_scores, out_ids, out_rank, out_count,
                                     out_flags);
 }
 
@@ -3382,6 +3361,52 @@ TailWorkspace carve_tail(void* base, const armi_index* tail, int nq, int k) {
   w.g_ws = cv.take<char>(w.g_ws_bytes);
   w.bytes = cv.off + 256;
   return w;
+}
+
+// The launches of armi_dense_tail_topk (q_mask null: row_masks is the call's one mask or null)
+// and armi_dense_tail_topk_qmask; arguments checked by the entry points.
+template <int DIM>
+int dense_tail_launch(const armi_index* tail, const uint16_t* queries, int nq, int k,
+                      const uint64_t* row_masks, int64_t mask_stride, const int32_t* q_mask,
+                      int n_masks, const int64_t* main_ids, const double* main_rank,
+                      const int32_t* main_count, float* out_scores, int64_t* out_ids,
+                      double* out_rank, int32_t* out_count, uint32_t* out_flags,
+                      const TailWorkspace& w, hipStream_t stream) {
+  const QMask qm{q_mask, mask_stride, n_masks, nq};
+  const int n_wg = tail_wgs(tail, false);
+  if (tail->n_rows > 0) {
+    const dim3 grid(n_wg, (nq + kQB - 1) / kQB);
+    if (q_mask) {
+      if (int rc = allow_lds(dense_tail_scan_qmask_kernel<DIM>, tail_scan_lds_bytes<DIM>()))
+        return rc;
+      dense_tail_scan_qmask_kernel<DIM><<<grid, dim3(kThreads), tail_scan_lds_bytes<DIM>(), stream>>>(
+          tail->rows, tail->inv_norm32, row_masks, q_mask, n_masks, mask_stride, tail->n_rows,
+          tail->n_tiles, queries, nq, k, main_rank, main_count, w.wg_cnt, w.wg_list);
+      ARMI_LAUNCHED("dense_tail_scan_qmask_kernel");
+    } else {
+      if (int rc = allow_lds(dense_tail_scan_kernel<DIM>, tail_scan_lds_bytes<DIM>())) return rc;
+      dense_tail_scan_kernel<DIM><<<grid, dim3(kThreads), tail_scan_lds_bytes<DIM>(), stream>>>(
+          tail->rows, tail->inv_norm32, row_masks, tail->n_rows, tail->n_tiles, queries, nq, k,
+          main_rank, main_count, w.wg_cnt, w.wg_list);
+      ARMI_LAUNCHED("dense_tail_scan_kernel");
+    }
+  }
+  const int n_lists = tail->n_rows > 0 ? n_wg : 0;
+  if (q_mask) {
+    dense_tail_finish_qmask_kernel<DIM><<<dim3(nq), dim3(kDenseMergeThreads), kTailFinishLds,
+                                          stream>>>(
+        w.wg_cnt, w.wg_list, n_lists, tail->rows, tail->inv_norm, tail->norm2, row_masks, qm,
+        tail->n_rows, queries, k, tail->ordinal_base, main_ids, main_rank, main_count, out_scores,
+        out_ids, out_rank, out_count, out_flags);
+    ARMI_LAUNCHED("dense_tail_finish_qmask_kernel");
+  } else {
+    dense_tail_finish_kernel<DIM><<<dim3(nq), dim3(kDenseMergeThreads), kTailFinishLds, stream>>>(
+        w.wg_cnt, w.wg_list, n_lists, tail->rows, tail->inv_norm, tail->norm2, row_masks,
+        tail->n_rows, queries, k, tail->ordinal_base, main_ids, main_rank, main_count, out_scores,
+        out_ids, out_rank, out_count, out_flags);
+    ARMI_LAUNCHED("dense_tail_finish_kernel");
+  }
+  return ARMI_OK;
 }
 
 // ------------------------------------------------------------------------ row-list top-k
@@ -3506,11 +3531,37 @@ int dispatch_dim(int dim, F&& f) {
   }
 }
 
+// armi_dense_topk and armi_dense_topk_qmask after their argument checks (f.img is set here).
+// Workspace layout: [carved buffers][rank scratch nq*k doubles][flags nq u32], behind the mask
+// image for a per-query-mask call; an empty index answers with the call's flag word alone.
+int dense_topk_checked(const armi_index* idx, const uint16_t* queries, int nq, int k, DenseFilter f,
+                       float* out_scores, int64_t* out_ids, double* out_rank, int32_t* out_count,
+                       uint32_t* out_flags, void* workspace, hipStream_t stream) {
+  const bool qmask = f.qm.q_mask != nullptr;
+  ARMI_HIP(hipSetDevice(idx->device));
+  if (idx->n_rows == 0) {
+    ARMI_HIP(hipMemsetAsync(out_count, 0, sizeof(int32_t) * nq, stream));
+    ARMI_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out_flags),
+                               qmask ? (int)ARMI_FLAG_QMASK : 0, nq, stream));
+    ARMI_HIP(hipMemsetAsync(out_ids, 0xff, sizeof(int64_t) * nq * k, stream));
+    return ARMI_OK;
+  }
+  char* base = static_cast<char*>(workspace);
+  if (qmask) base += qmask_img_bytes(idx, nq);
+  const Workspace w = carve(base, idx, nq, k, true);
+  f.img = qmask ? workspace : static_cast<void*>(w.mask_img);
+  if (!out_rank) out_rank = reinterpret_cast<double*>(base + armi::align_up(w.bytes, 256));
+  return dispatch_dim(idx->dim, [&](auto D) {
+    constexpr int DIM = decltype(D)::value;
+    return dense_topk_impl<DIM>(idx, queries, nq, k, f, out_scores, out_ids, out_rank, out_count,
+                                out_flags, w, stream);
+  });
+}
+
 }  // namespace
 
 extern "C" {
 
-// Workspace layout: [carved buffers][rank scratch nq*k doubles][flags nq u32]
 int armi_dense_scan_form(const armi_index* idx, int n_queries, int k) {
   if (!idx || n_queries <= 0 || k <= 0) return -1;
   k = std::min(k, kMaxK);
@@ -3545,22 +3596,8 @@ int armi_dense_topk(const armi_index* idx, const uint16_t* queries, int n_querie
                "armi_dense_topk: null pointer argument");
   ARMI_REQUIRE(workspace_bytes >= armi_dense_workspace_bytes(idx, n_queries, k),
                "armi_dense_topk: workspace too small");
-  ARMI_HIP(hipSetDevice(idx->device));
-  if (idx->n_rows == 0) {
-    ARMI_HIP(hipMemsetAsync(out_count, 0, sizeof(int32_t) * n_queries, stream));
-    ARMI_HIP(hipMemsetAsync(out_flags, 0, sizeof(uint32_t) * n_queries, stream));
-    ARMI_HIP(hipMemsetAsync(out_ids, 0xff, sizeof(int64_t) * n_queries * k, stream));
-    return ARMI_OK;
-  }
-  const Workspace w = carve(workspace, idx, n_queries, k, true);
-  double* rank = out_rank;
-  if (!rank)
-    rank = reinterpret_cast<double*>(static_cast<char*>(workspace) + armi::align_up(w.bytes, 256));
-  return dispatch_dim(idx->dim, [&](auto D) {
-    constexpr int DIM = decltype(D)::value;
-    return dense_topk_impl<DIM>(idx, queries, n_queries, k, row_mask, out_scores, out_ids, rank,
-                                out_count, out_flags, w, stream);
-  });
+  return dense_topk_checked(idx, queries, n_queries, k, DenseFilter{row_mask, QMask{}, nullptr},
+                            out_scores, out_ids, out_rank, out_count, out_flags, workspace, stream);
 }
 
 int armi_dense_qmask_supported(const armi_index* idx, int n_queries, int k) {
@@ -3593,26 +3630,9 @@ int armi_dense_topk_qmask(const armi_index* idx, const uint16_t* queries, int n_
                "armi_dense_topk_qmask: null pointer argument");
   ARMI_REQUIRE(workspace_bytes >= armi_dense_qmask_workspace_bytes(idx, n_queries, k, n_masks),
                "armi_dense_topk_qmask: workspace too small");
-  ARMI_HIP(hipSetDevice(idx->device));
-  if (idx->n_rows == 0) {
-    ARMI_HIP(hipMemsetAsync(out_count, 0, sizeof(int32_t) * n_queries, stream));
-    ARMI_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out_flags), (int)ARMI_FLAG_QMASK,
-                               n_queries, stream));
-    ARMI_HIP(hipMemsetAsync(out_ids, 0xff, sizeof(int64_t) * n_queries * k, stream));
-    return ARMI_OK;
-  }
-  char* base = static_cast<char*>(workspace);
-  uint32_t* mask_img = reinterpret_cast<uint32_t*>(base);
-  base += qmask_img_bytes(idx, n_queries);
-  const Workspace w = carve(base, idx, n_queries, k, true);
-  double* rank = out_rank;
-  if (!rank) rank = reinterpret_cast<double*>(base + armi::align_up(w.bytes, 256));
-  return dispatch_dim(idx->dim, [&](auto D) {
-    constexpr int DIM = decltype(D)::value;
-    return dense_topk_qmask_impl<DIM>(idx, queries, n_queries, k, row_masks, mask_stride_words,
-                                      q_mask, n_masks, mask_img, out_scores, out_ids, rank,
-                                      out_count, out_flags, w, stream);
-  });
+  const QMask qm{q_mask, mask_stride_words, n_masks, n_queries};
+  return dense_topk_checked(idx, queries, n_queries, k, DenseFilter{row_masks, qm, nullptr},
+                            out_scores, out_ids, out_rank, out_count, out_flags, workspace, stream);
 }
 
 size_t armi_dense_exact_workspace_bytes(const armi_index* idx, int n_queries, int k) {
@@ -3697,22 +3717,9 @@ int armi_dense_tail_topk(const armi_index* tail, const uint16_t* queries, int n_
                                   out_scores, out_ids, out_count, stream);
   }
   return dispatch_dim(tail->dim, [&](auto D) {
-    constexpr int DIM = decltype(D)::value;
-    const int n_wg = tail_wgs(tail, false);
-    if (tail->n_rows > 0) {
-      if (int rc = allow_lds(dense_tail_scan_kernel<DIM>, tail_scan_lds_bytes<DIM>())) return rc;
-      dense_tail_scan_kernel<DIM><<<dim3(n_wg, (nq + kQB - 1) / kQB), dim3(kThreads),
-                                    tail_scan_lds_bytes<DIM>(), stream>>>(
-          tail->rows, tail->inv_norm32, tail_row_mask, tail->n_rows, tail->n_tiles, queries, nq, k,
-          main_rank, main_count, w.wg_cnt, w.wg_list);
-      ARMI_LAUNCHED("dense_tail_scan_kernel");
-    }
-    dense_tail_finish_kernel<DIM><<<dim3(nq), dim3(kDenseMergeThreads), kTailFinishLds, stream>>>(
-        w.wg_cnt, w.wg_list, tail->n_rows > 0 ? n_wg : 0, tail->rows, tail->inv_norm, tail->norm2,
-        tail_row_mask, tail->n_rows, queries, k, tail->ordinal_base, main_ids, main_rank,
-        main_count, out_scores, out_ids, out_rank, out_count, out_flags);
-    ARMI_LAUNCHED("dense_tail_finish_kernel");
-    return ARMI_OK;
+    return dense_tail_launch<decltype(D)::value>(tail, queries, nq, k, tail_row_mask, 0, nullptr, 0,
+                                                 main_ids, main_rank, main_count, out_scores,
+                                                 out_ids, out_rank, out_count, out_flags, w, stream);
   });
 }
 
@@ -3743,27 +3750,11 @@ int armi_dense_tail_topk_qmask(const armi_index* tail, const uint16_t* queries, 
                "armi_dense_tail_topk_qmask: outputs must not alias the main list");
   ARMI_HIP(hipSetDevice(tail->device));
   const TailWorkspace w = carve_tail(workspace, tail, n_queries, k);
-  const int nq = n_queries;
   return dispatch_dim(tail->dim, [&](auto D) {
-    constexpr int DIM = decltype(D)::value;
-    const int n_wg = tail_wgs(tail, false);
-    if (tail->n_rows > 0) {
-      if (int rc = allow_lds(dense_tail_scan_qmask_kernel<DIM>, tail_scan_lds_bytes<DIM>()))
-        return rc;
-      dense_tail_scan_qmask_kernel<DIM><<<dim3(n_wg, (nq + kQB - 1) / kQB), dim3(kThreads),
-                                          tail_scan_lds_bytes<DIM>(), stream>>>(
-          tail->rows, tail->inv_norm32, tail_row_masks, q_mask, n_masks, mask_stride_words,
-          tail->n_rows, tail->n_tiles, queries, nq, k, main_rank, main_count, w.wg_cnt, w.wg_list);
-      ARMI_LAUNCHED("dense_tail_scan_qmask_kernel");
-    }
-    dense_tail_finish_qmask_kernel<DIM><<<dim3(nq), dim3(kDenseMergeThreads), kTailFinishLds,
-                                          stream>>>(
-        w.wg_cnt, w.wg_list, tail->n_rows > 0 ? n_wg : 0, tail->rows, tail->inv_norm, tail->norm2,
-        tail_row_masks, q_mask, n_masks, mask_stride_words, tail->n_rows, queries, k,
-        tail->ordinal_base, main_ids, main_rank, main_count, out_scores, out_ids, out_rank,
-        out_count, out_flags);
-    ARMI_LAUNCHED("dense_tail_finish_qmask_kernel");
-    return ARMI_OK;
+    return dense_tail_launch<decltype(D)::value>(tail, queries, n_queries, k, tail_row_masks,
+                                                 mask_stride_words, q_mask, n_masks, main_ids,
+                                                 main_rank, main_count, out_scores, out_ids,
+                                                 out_rank, out_count, out_flags, w, stream);
   });
 }
 

@@ -45,6 +45,8 @@ namespace {
 using armi::kNegInfD;
 using armi::kNoOrd;
 using armi::kRowlistChunk;
+using armi::QMask;  // one row mask per query (armi_index.h)
+using armi::qmask_row;
 
 constexpr int kQB = 64;                 // queries per pass
 constexpr int kQW = 4;                  // queries per wave
@@ -666,22 +668,6 @@ __device__ __forceinline__ int2 range_cursor(int32_t t, int g, int64_t lo, int n
     c = a;
   }
   return make_int2(c, post[c].x);
-}
-
-// One row mask per query (armi_sparse_topk_qmask): query q of the pass (q_mask already points at
-// the pass's first query) is filtered by row q_mask[q] of the caller's [n_masks][stride] stack of
-// ordinal bitmasks; -1, and any value outside [0, n_masks), is unfiltered and indexes nothing.
-struct QMask {
-  const int32_t* q_mask;
-  int64_t stride;
-  int n_masks;
-  int nq;  // queries of the pass
-};
-__device__ __forceinline__ const uint64_t* qmask_row(const uint64_t* __restrict__ row_masks,
-                                                      const QMask& qm, int q) {
-  if (q < 0 || q >= qm.nq) return nullptr;
-  const int32_t m = qm.q_mask[q];
-  return m >= 0 && m < qm.n_masks ? row_masks + (size_t)m * qm.stride : nullptr;
 }
 
 // Workgroup = one row range; steps = (256-row tile, segment of kU = 64 pass terms). Staging: term

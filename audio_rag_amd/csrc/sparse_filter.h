@@ -500,12 +500,8 @@ __device__ __forceinline__ void sparse_filter_scan_body(
   auto tile_hi = [&](int tile) { return (int32_t)min(lo + (int64_t)(tile + 1) * kFT, hi); };
   // per-query masks: the mask of the lane's query column in each half (-1: unfiltered), and
   // whether the pass has a filtered query at all
-  auto mask_of = [&](int q) {
-    const int32_t m = q < qm.nq ? qm.q_mask[q] : -1;
-    return m >= 0 && m < qm.n_masks ? m : -1;
-  };
   bool any_mask = false;  // workgroup-uniform: every wave looks at all 64 queries
-  if constexpr (kQM) any_mask = __ballot(mask_of(lane) >= 0) != 0ull;
+  if constexpr (kQM) any_mask = __ballot(armi::qmask_index(qm, lane) >= 0) != 0ull;
   // step s's loads into ring slot `slot`: every lane issues the same two loads per step (steps
   // past the end and absent terms read a fixed in-bounds address), so the waits the compiler
   // counts stay exact
@@ -700,7 +696,7 @@ __device__ __forceinline__ void sparse_filter_scan_body(
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         __builtin_amdgcn_sched_barrier(0);
-        const int32_t mq = any_mask ? mask_of(32 * h + (lane & 31)) : -1;
+        const int32_t mq = any_mask ? armi::qmask_index(qm, 32 * h + (lane & 31)) : -1;
         const uint32_t* mrow32 =
             reinterpret_cast<const uint32_t*>(row_mask + (size_t)max(mq, 0) * qm.stride);
 #pragma unroll

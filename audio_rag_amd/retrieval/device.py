@@ -120,6 +120,15 @@ def _check_row_lists(list_ptr: torch.Tensor, list_rows: torch.Tensor, q_list: to
     return n_lists
 
 
+def _check_row_mask(row_mask: torch.Tensor | None, n_rows: int) -> None:
+    """The one shared mask of DenseIndex.topk and TailIndex.tail_topk (None: no filter)."""
+    if row_mask is None:
+        return
+    need = (n_rows + 63) // 64
+    if row_mask.dtype != torch.int64 or row_mask.numel() < need or not row_mask.is_cuda:
+        raise ValueError(f"row_mask must be an int64 device tensor of >= {need} words")
+
+
 def _check_row_masks(row_masks: torch.Tensor, q_mask: torch.Tensor, n_queries: int,
                      n_rows: int) -> tuple[int, int]:
     """Argument checks of DenseIndex.topk_masks and SparseIndex.topk_masks (include/armi.h); returns
@@ -231,10 +240,7 @@ class DenseIndex:
         _check_k(k)
         b = int(queries.shape[0])
         dev = self.device
-        if row_mask is not None:
-            need = (self.n_rows + 63) // 64
-            if row_mask.dtype != torch.int64 or row_mask.numel() < need or not row_mask.is_cuda:
-                raise ValueError(f"row_mask must be an int64 device tensor of >= {need} words")
+        _check_row_mask(row_mask, self.n_rows)
         if out is None:
             out = TopK.empty(b, k, dev, rank=True)
         workspace = _workspace(workspace, self.workspace_bytes(max(b, 1), k, exact), dev)
@@ -352,31 +358,42 @@ class TailIndex(DenseIndex):
     def tail_workspace_bytes(self, n_queries: int, k: int) -> int:
         return int(query("armi_dense_tail_workspace_bytes", self._handle, n_queries, k))
 
-    def tail_topk(self, queries: torch.Tensor, k: int, main: TopK,
-                  row_mask: torch.Tensor | None = None,
-                  workspace: torch.Tensor | None = None) -> TopK:
-        """The top-k over the main index and this segment, from `main` = the main index's
-        topk(queries, k) (armi_dense_tail_topk). row_mask: bit r = row r of this segment."""
+    def _tail_pass(self, queries: torch.Tensor, k: int, main: TopK,
+                   workspace: torch.Tensor | None, row_mask: torch.Tensor | None = None,
+                   row_masks: torch.Tensor | None = None,
+                   q_mask: torch.Tensor | None = None) -> TopK:
+        """The body of tail_topk (row_masks None: one mask or none) and tail_topk_masks."""
         _check_fp16_2d(queries, "queries", self.dim)
         _check_k(k)
         b = int(queries.shape[0])
         if tuple(main.ids.shape) != (b, k):
             raise ValueError("main must be the main index's top-k of the same queries and k")
         dev = self.device
-        if row_mask is not None:
-            need = (self.n_rows + 63) // 64
-            if row_mask.dtype != torch.int64 or row_mask.numel() < need or not row_mask.is_cuda:
-                raise ValueError(f"row_mask must be an int64 device tensor of >= {need} words")
+        if row_masks is None:
+            _check_row_mask(row_mask, self.n_rows)
+            fn, masks = "armi_dense_tail_topk", (ptr(row_mask),)
+        else:
+            n_masks, stride = _check_row_masks(row_masks, q_mask, b, self.n_rows)
+            q_mask = _on_device(q_mask, dev)
+            fn, masks = "armi_dense_tail_topk_qmask", (ptr(row_masks) if n_masks else None, stride,
+                                                       ptr(q_mask), n_masks)
         out = TopK.empty(b, k, dev, rank=True)
         if b == 0:
             return out
         workspace = _workspace(workspace, self.tail_workspace_bytes(b, k), dev)
         m_scores, m_ids, m_rank, m_count = (t.contiguous() for t in
                                             (main.scores, main.ids, main.rank, main.count))
-        call("armi_dense_tail_topk", self._handle, ptr(queries), b, k, ptr(row_mask), ptr(m_scores),
-             ptr(m_ids), ptr(m_rank), ptr(m_count), ptr(out.scores), ptr(out.ids), ptr(out.rank),
-             ptr(out.count), ptr(out.flags), ptr(workspace), workspace.numel(), stream_handle())
+        call(fn, self._handle, ptr(queries), b, k, *masks, ptr(m_scores), ptr(m_ids), ptr(m_rank),
+             ptr(m_count), ptr(out.scores), ptr(out.ids), ptr(out.rank), ptr(out.count),
+             ptr(out.flags), ptr(workspace), workspace.numel(), stream_handle())
         return out
+
+    def tail_topk(self, queries: torch.Tensor, k: int, main: TopK,
+                  row_mask: torch.Tensor | None = None,
+                  workspace: torch.Tensor | None = None) -> TopK:
+        """The top-k over the main index and this segment, from `main` = the main index's
+        topk(queries, k) (armi_dense_tail_topk). row_mask: bit r = row r of this segment."""
+        return self._tail_pass(queries, k, main, workspace, row_mask=row_mask)
 
     def tail_topk_masks(self, queries: torch.Tensor, k: int, main: TopK, row_masks: torch.Tensor,
                         q_mask: torch.Tensor, workspace: torch.Tensor | None = None) -> TopK:
@@ -386,25 +403,7 @@ class TailIndex(DenseIndex):
         tensor is uploaded). `main` = the main index's list of the same queries and k, each query
         under its own filter (DenseIndex.topk_masks). The same answer as tail_topk(row_mask=...)
         called once per mask; flags carry ARMI_FLAG_QMASK. Any k that tail_topk takes."""
-        _check_fp16_2d(queries, "queries", self.dim)
-        _check_k(k)
-        b = int(queries.shape[0])
-        if tuple(main.ids.shape) != (b, k):
-            raise ValueError("main must be the main index's top-k of the same queries and k")
-        dev = self.device
-        n_masks, stride = _check_row_masks(row_masks, q_mask, b, self.n_rows)
-        q_mask = _on_device(q_mask, dev)
-        out = TopK.empty(b, k, dev, rank=True)
-        if b == 0:
-            return out
-        workspace = _workspace(workspace, self.tail_workspace_bytes(b, k), dev)
-        m_scores, m_ids, m_rank, m_count = (t.contiguous() for t in
-                                            (main.scores, main.ids, main.rank, main.count))
-        call("armi_dense_tail_topk_qmask", self._handle, ptr(queries), b, k,
-             ptr(row_masks) if n_masks else None, stride, ptr(q_mask), n_masks, ptr(m_scores),
-             ptr(m_ids), ptr(m_rank), ptr(m_count), ptr(out.scores), ptr(out.ids), ptr(out.rank),
-             ptr(out.count), ptr(out.flags), ptr(workspace), workspace.numel(), stream_handle())
-        return out
+        return self._tail_pass(queries, k, main, workspace, row_masks=row_masks, q_mask=q_mask)
 
 
 class SparseIndex:
@@ -626,13 +625,11 @@ class TailSparseIndex:
     def tail_workspace_bytes(self, n_queries: int, k: int) -> int:
         return int(query("armi_sparse_tail_workspace_bytes", self.n_rows, n_queries, k))
 
-    def tail_topk(self, q_indptr: torch.Tensor, q_indices: torch.Tensor, q_values: torch.Tensor,
-                  k: int, main: TopK, row_mask: torch.Tensor | None = None,
-                  workspace: torch.Tensor | None = None) -> TopK:
-        """The top-k over the main index and this segment, from `main` = the main SparseIndex's
-        topk of the same queries and k (armi_sparse_tail_topk). row_mask: bit r = row r of this
-        segment. ARMI_TAIL_PASS=general (read per call) computes the same answer by topk() over
-        the tail and a merge of the two lists."""
+    def _tail_pass(self, q_indptr: torch.Tensor, q_indices: torch.Tensor, q_values: torch.Tensor,
+                   k: int, main: TopK, workspace: torch.Tensor | None,
+                   row_mask: torch.Tensor | None = None, row_masks: torch.Tensor | None = None,
+                   q_mask: torch.Tensor | None = None) -> TopK:
+        """The body of tail_topk (row_masks None: one mask or none) and tail_topk_masks."""
         _check_k(k)
         _check_query_csr(q_indptr, q_indices, q_values)
         b = int(q_indptr.numel()) - 1
@@ -641,19 +638,28 @@ class TailSparseIndex:
         self._check_main(main, b, k, dev)
         if q_indptr.device != dev:
             raise ValueError(f"the query CSR must live on {dev}")
-        if row_mask is not None:
-            need = (n_rows + 63) // 64
-            if row_mask.dtype != torch.int64 or row_mask.numel() < need or \
-                    row_mask.device != dev or not row_mask.is_contiguous():
-                raise ValueError(f"row_mask must be a contiguous int64 tensor of >= {need} words "
-                                 f"on {dev}")
-        if os.environ.get("ARMI_TAIL_PASS", "")[:1] == "g":
-            t = self.topk(q_indptr, q_indices, q_values, k, row_mask=row_mask)
-            scores = torch.stack([main.scores, t.scores])
-            m = merge_shards(scores.double(), scores, torch.stack([main.ids, t.ids]),
-                             torch.stack([main.count, t.count]), k)
-            m.flags = main.flags
-            return m
+        if row_masks is not None:
+            n_masks, stride = _check_row_masks(row_masks, q_mask, b, n_rows)
+            if row_masks.device != dev:
+                raise ValueError(f"row_masks must live on {dev}")
+            q_mask = _on_device(q_mask, dev)
+            fn, masks = "armi_sparse_tail_topk_qmask", (ptr(row_masks) if n_masks else None, stride,
+                                                        ptr(q_mask), n_masks)
+        else:
+            if row_mask is not None:
+                need = (n_rows + 63) // 64
+                if row_mask.dtype != torch.int64 or row_mask.numel() < need or \
+                        row_mask.device != dev or not row_mask.is_contiguous():
+                    raise ValueError(f"row_mask must be a contiguous int64 tensor of >= {need} "
+                                     f"words on {dev}")
+            if os.environ.get("ARMI_TAIL_PASS", "")[:1] == "g":
+                t = self.topk(q_indptr, q_indices, q_values, k, row_mask=row_mask)
+                scores = torch.stack([main.scores, t.scores])
+                m = merge_shards(scores.double(), scores, torch.stack([main.ids, t.ids]),
+                                 torch.stack([main.count, t.count]), k)
+                m.flags = main.flags
+                return m
+            fn, masks = "armi_sparse_tail_topk", (ptr(row_mask),)
         out = TopK.empty(b, k, dev, rank=False)
         if b == 0:
             return out
@@ -662,12 +668,22 @@ class TailSparseIndex:
         m_scores, m_ids, m_count = (t.contiguous() for t in (main.scores, main.ids, main.count))
         m_flags = None if main.flags is None else main.flags.contiguous()
         with torch.cuda.device(dev):
-            call("armi_sparse_tail_topk", ptr(indptr), ptr(indices), ptr(values), n_rows,
-                 self.ordinal_base, ptr(q_indptr), ptr(q_indices), ptr(q_values), b, k,
-                 ptr(row_mask), ptr(m_scores), ptr(m_ids), ptr(m_count), ptr(m_flags),
-                 ptr(out.scores), ptr(out.ids), ptr(out.count), ptr(out.flags), ptr(workspace),
-                 workspace.numel(), stream_handle())
+            call(fn, ptr(indptr), ptr(indices), ptr(values), n_rows, self.ordinal_base,
+                 ptr(q_indptr), ptr(q_indices), ptr(q_values), b, k, *masks, ptr(m_scores),
+                 ptr(m_ids), ptr(m_count), ptr(m_flags), ptr(out.scores), ptr(out.ids),
+                 ptr(out.count), ptr(out.flags), ptr(workspace), workspace.numel(),
+                 stream_handle())
         return out
+
+    def tail_topk(self, q_indptr: torch.Tensor, q_indices: torch.Tensor, q_values: torch.Tensor,
+                  k: int, main: TopK, row_mask: torch.Tensor | None = None,
+                  workspace: torch.Tensor | None = None) -> TopK:
+        """The top-k over the main index and this segment, from `main` = the main SparseIndex's
+        topk of the same queries and k (armi_sparse_tail_topk). row_mask: bit r = row r of this
+        segment. ARMI_TAIL_PASS=general (read per call) computes the same answer by topk() over
+        the tail and a merge of the two lists."""
+        return self._tail_pass(q_indptr, q_indices, q_values, k, main, workspace,
+                               row_mask=row_mask)
 
     @staticmethod
     def _check_main(main: TopK, b: int, k: int, dev: torch.device) -> None:
@@ -691,33 +707,8 @@ class TailSparseIndex:
         tensor is uploaded). `main` = the main SparseIndex's list of the same queries and k, each
         query under its own filter (SparseIndex.topk_masks); its flags pass through. The same
         answer as tail_topk(row_mask=...) called once per mask."""
-        _check_k(k)
-        _check_query_csr(q_indptr, q_indices, q_values)
-        b = int(q_indptr.numel()) - 1
-        indptr, indices, values, n_rows = self._csr
-        dev = indptr.device
-        self._check_main(main, b, k, dev)
-        if q_indptr.device != dev:
-            raise ValueError(f"the query CSR must live on {dev}")
-        n_masks, stride = _check_row_masks(row_masks, q_mask, b, n_rows)
-        if row_masks.device != dev:
-            raise ValueError(f"row_masks must live on {dev}")
-        q_mask = _on_device(q_mask, dev)
-        out = TopK.empty(b, k, dev, rank=False)
-        if b == 0:
-            return out
-        need = int(query("armi_sparse_tail_workspace_bytes", n_rows, b, k))
-        workspace = _workspace(workspace, need, dev)
-        m_scores, m_ids, m_count = (t.contiguous() for t in (main.scores, main.ids, main.count))
-        m_flags = None if main.flags is None else main.flags.contiguous()
-        with torch.cuda.device(dev):
-            call("armi_sparse_tail_topk_qmask", ptr(indptr), ptr(indices), ptr(values), n_rows,
-                 self.ordinal_base, ptr(q_indptr), ptr(q_indices), ptr(q_values), b, k,
-                 ptr(row_masks) if n_masks else None, stride, ptr(q_mask), n_masks, ptr(m_scores),
-                 ptr(m_ids), ptr(m_count), ptr(m_flags), ptr(out.scores), ptr(out.ids),
-                 ptr(out.count), ptr(out.flags), ptr(workspace), workspace.numel(),
-                 stream_handle())
-        return out
+        return self._tail_pass(q_indptr, q_indices, q_values, k, main, workspace,
+                               row_masks=row_masks, q_mask=q_mask)
 
     rowlist_workspace_bytes = staticmethod(SparseIndex.rowlist_workspace_bytes)
     topk_rows = SparseIndex.topk_rows  # reads indptr / indices / values / n_rows / ordinal_base
