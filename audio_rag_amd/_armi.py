@@ -29,6 +29,7 @@ TIMING_DENSE_SCAN, TIMING_SPARSE_SCAN, TIMING_ENCODER_GEMM, TIMING_SPARSE_STAGE 
 TIMING_QMASK_PREP = 4
 SCAN_FP16, SCAN_INT8_FILTER, SCAN_TILED_FP16, SCAN_TILED_INT8 = 0, 1, 2, 3  # armi_dense_scan_form
 ABI_VERSION = 6
+ARMI_STREAM_QUERY_MASKS = 1  # armi_stream_create_ex flag: one filter per request inside a batch
 
 c_void_p = ctypes.c_void_p
 c_int = ctypes.c_int
@@ -90,6 +91,9 @@ SIGNATURES: dict[str, tuple] = {
     "armi_dense_topk_qmask": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p,
                                       c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_size_t, c_void_p]),
+    "armi_dense_topk_qmask_ptrs": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                           c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_size_t, c_void_p]),
     "armi_dense_exact_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "armi_dense_exact_topk": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -108,6 +112,8 @@ SIGNATURES: dict[str, tuple] = {
     "armi_stream_create": (c_int, [c_void_p, c_int, c_int, ctypes.c_double, ctypes.POINTER(c_void_p)]),
     "armi_stream_create_hybrid": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_double,
                                           ctypes.POINTER(c_void_p)]),
+    "armi_stream_create_ex": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_double,
+                                      ctypes.c_uint, ctypes.POINTER(c_void_p)]),
     "armi_stream_destroy": (c_int, [c_void_p]),
     "armi_stream_stop": (c_int, [c_void_p]),
     "armi_stream_submit": (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_int64)]),
@@ -118,6 +124,12 @@ SIGNATURES: dict[str, tuple] = {
     "armi_stream_wait": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  ctypes.c_double]),
     "armi_stream_stats": (c_int, [c_void_p, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),
+    "armi_stream_stats_ex": (c_int, [c_void_p, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64),
+                                     ctypes.POINTER(c_int64)]),
+    "armi_stream_loadgen_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                       c_int64, ctypes.c_double, ctypes.c_uint64, c_void_p, c_int64,
+                                       c_void_p, ctypes.POINTER(ctypes.c_double),
+                                       ctypes.POINTER(c_int64), c_void_p, c_void_p]),
     "armi_stream_loadgen": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                     ctypes.c_double, ctypes.c_uint64, c_void_p,
                                     ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int64),
@@ -132,6 +144,9 @@ SIGNATURES: dict[str, tuple] = {
     "armi_sparse_topk_qmask": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                        c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_size_t, c_void_p]),
+    "armi_sparse_topk_qmask_ptrs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                            c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_size_t, c_void_p]),
     "armi_rrf_fuse": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                               c_void_p, c_void_p, c_void_p, c_void_p]),
     "armi_enc_layernorm_residual": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,

@@ -105,6 +105,13 @@ constexpr float kTwoPow24 = 16777216.0f;
 // [n_masks][stride] stack of ordinal bitmasks; -1, and any value outside [0, n_masks), is
 // unfiltered and indexes nothing; a query outside [0, nq) is unfiltered too, and q_mask is not
 // read for it. This is the only place that decides it.
+// The masks reach a kernel in one of two forms, a template argument of its per-query-mask
+// instance (kTable): the stack above, or (the *_qmask_ptrs entry points) a device table of n_masks
+// mask pointers, each its own allocation of at least ceil(rows / 64) words, a null entry being
+// "unfiltered". The table travels in the stack's argument (qmask_table), stride is unused, and
+// qmask_row is the one helper that yields a query's mask from either. With one allocation per mask
+// nothing may be read at or past word ceil(rows / 64) of a row qmask_row returned: DESIGN.md
+// section 17 lists every load and the bound that keeps it below.
 struct QMask {
   const int32_t* q_mask;
   int64_t stride;
@@ -116,10 +123,22 @@ __device__ __forceinline__ int32_t qmask_index(const QMask& qm, int q) {
   const int32_t m = q >= 0 && q < qm.nq ? qm.q_mask[q] : -1;
   return m >= 0 && m < qm.n_masks ? m : -1;
 }
-// the query's row of the stack, or null: unfiltered
+// a mask table as the kernels' mask argument, and back
+inline const uint64_t* qmask_table(const uint64_t* const* mask_ptrs) {
+  return reinterpret_cast<const uint64_t*>(mask_ptrs);
+}
+// mask number m >= 0 of the call: its row of the stack, or its table entry (null: unfiltered)
+template <bool kTable = false>
+__device__ __forceinline__ const uint64_t* qmask_row_of(const uint64_t* __restrict__ row_masks,
+                                                         const QMask& qm, int32_t m) {
+  if constexpr (kTable) return reinterpret_cast<const uint64_t* const*>(row_masks)[m];
+  else return row_masks + (size_t)m * qm.stride;
+}
+// the query's mask (its row of the stack, or its entry of the table), or null: unfiltered
+template <bool kTable = false>
 __device__ __forceinline__ const uint64_t* qmask_row(const uint64_t* __restrict__ row_masks,
                                                       const QMask& qm, int q) {
   const int32_t m = qmask_index(qm, q);
-  return m >= 0 ? row_masks + (size_t)m * qm.stride : nullptr;
+  return m >= 0 ? qmask_row_of<kTable>(row_masks, qm, m) : nullptr;
 }
 }  // namespace armi

@@ -2236,7 +2236,7 @@ __device__ void collect_top_rows(const int32_t* __restrict__ list, int64_t r0, i
   });
 }
 
-template <int DIM>
+template <int DIM, bool kTable = false>
 __device__ __forceinline__ void collect_merge_body(
     const int bid, const int n_help, const int32_t* __restrict__ col_cnt, int32_t* __restrict__ col_list, int col_cap,
     int32_t* __restrict__ help_done, int nq, const uint16_t* __restrict__ rows,
@@ -2256,9 +2256,11 @@ __device__ __forceinline__ void collect_merge_body(
                       out_count);
     if (tid == 0) flags[qg] = ARMI_FLAG_FALLBACK | flag_or;
   };
-  // qm.q_mask (armi_dense_topk_qmask): row_mask is the call's stack of masks and the helpers
-  // filter by the query's own row of it (qmask_row)
-  auto mask_of = [&](int qg) { return qm.q_mask ? qmask_row(row_mask, qm, qg) : row_mask; };
+  // qm.q_mask (armi_dense_topk_qmask, _ptrs): row_mask is the call's stack of masks (kTable: its
+  // table of mask pointers) and the helpers filter by the query's own mask (qmask_row)
+  auto mask_of = [&](int qg) {
+    return qm.q_mask ? qmask_row<kTable>(row_mask, qm, qg) : row_mask;
+  };
   if (bid < nq) {  // the query's own workgroup
     const int qg = bid;
     if (flags[qg] & ARMI_FLAG_CERTIFIED) {  // workgroup-uniform
@@ -2324,8 +2326,9 @@ __global__ __launch_bounds__(kDenseMergeThreads) void dense_collect_merge_kernel
 // The same for armi_dense_topk_qmask: the helpers of an overflowed query filter by that query's
 // own mask, and every query's flag word gets flag_or (ARMI_FLAG_QMASK). (Like the other kernels
 // with a query count of their own, it takes the mask arguments loose and builds the QMask over
-// that count: the body's queries are then inside it by construction.)
-template <int DIM>
+// that count: the body's queries are then inside it by construction.) kTable
+// (armi_dense_topk_qmask_ptrs): row_masks carries the call's table of mask pointers.
+template <int DIM, bool kTable>
 __global__ __launch_bounds__(kDenseMergeThreads) void dense_collect_merge_qmask_kernel(
     const int32_t* __restrict__ col_cnt, int32_t* __restrict__ col_list, int col_cap,
     int32_t* __restrict__ help_done, int nq, const uint16_t* __restrict__ rows,
@@ -2336,7 +2339,7 @@ __global__ __launch_bounds__(kDenseMergeThreads) void dense_collect_merge_qmask_
     int64_t ordinal_base, float* __restrict__ out_scores, int64_t* __restrict__ out_ids,
     double* __restrict__ out_rank, int32_t* __restrict__ out_count, uint32_t* __restrict__ flags,
     uint32_t flag_or) {
-  collect_merge_body<DIM>(blockIdx.x, (int)gridDim.x - nq, col_cnt, col_list, col_cap, help_done, nq, rows,
+  collect_merge_body<DIM, kTable>(blockIdx.x, (int)gridDim.x - nq, col_cnt, col_list, col_cap, help_done, nq, rows,
       inv_norm, norm2, row_masks, n_rows, queries, inv_q, k, ordinal_base, out_scores, out_ids,
       out_rank, out_count, flags, QMask{q_mask, mask_stride, n_masks, nq}, flag_or);
 }
@@ -2351,10 +2354,12 @@ __global__ __launch_bounds__(kDenseMergeThreads) void dense_collect_merge_qmask_
 // per 64 queries left 49 workgroups at 100k rows, each thread walking 16 x 32 loads: 0.16 ms at
 // 100k and at 1M rows alike, latency, not bytes.)
 // Bits of ordinals >= n_rows and words of queries past nq are 0; a query without a mask
-// (qmask_row: null) gets every row below n_rows.
+// (qmask_row: null) gets every row below n_rows. kTable (armi_dense_topk_qmask_ptrs): row_masks
+// carries the call's table of mask pointers.
 constexpr int kPrepTiles = 64;
 constexpr int kPrepQueries = 16;
 static_assert(kQB % kPrepQueries == 0 && kPrepQueries % 4 == 0, "query groups of the prep grid");
+template <bool kTable>
 __global__ __launch_bounds__(256) void qmask_prep_kernel(
     const uint64_t* __restrict__ row_masks, int64_t mask_stride, const int32_t* __restrict__ q_mask,
     int n_masks, int nq, int64_t n_rows, int64_t T, int64_t perm_mul, uint32_t* __restrict__ out) {
@@ -2371,7 +2376,7 @@ __global__ __launch_bounds__(256) void qmask_prep_kernel(
     const int q = qb * kQB + c0 + c;
     uint32_t w = 0;
     if (q < nq && u < T) {
-      const uint64_t* mk = qmask_row(row_masks, qm, q);  // (wave-uniform)
+      const uint64_t* mk = qmask_row<kTable>(row_masks, qm, q);  // (wave-uniform)
 #pragma unroll
       for (int p = 0; p < TILE_ROWS; ++p) {
         const int64_t i = u + p * T;
@@ -2799,11 +2804,14 @@ int launch_exact(const armi_index* idx, const uint16_t* queries, int nq, int k,
 // row mask or null, and img the room for its image in int8 order (Workspace::mask_img, u64 words).
 // qm.q_mask set (armi_dense_topk_qmask): mask is the [n_masks][stride] stack, qm names each query's
 // row of it and img is the room for the call's mask image (qmask_prep_kernel, u32 words); every
-// stage that tests a mask then runs its per-query sibling.
+// stage that tests a mask then runs its per-query sibling. table (armi_dense_topk_qmask_ptrs): mask
+// carries the call's table of n_masks mask pointers instead of the stack (armi::qmask_table), and
+// the two kernels that read the caller's masks run their table instances.
 struct DenseFilter {
   const uint64_t* mask;
   QMask qm;
   void* img;
+  bool table = false;
 };
 
 // Second pass for the uncertified queries (both kernels exit at once when every query of the
@@ -2848,8 +2856,10 @@ int dense_second_pass(const armi_index* idx, const uint16_t* queries, int nq, in
   const int n_help = std::max(1, std::min<int>(kMaxHelp, kCollectCap / k));
   const dim3 grid(nq + n_help);
   if (qmask) {
-    if (int rc = allow_lds(dense_collect_merge_qmask_kernel<DIM>, kColMergeLds)) return rc;
-    dense_collect_merge_qmask_kernel<DIM><<<grid, dim3(kDenseMergeThreads), kColMergeLds, stream>>>(
+    auto kern = f.table ? dense_collect_merge_qmask_kernel<DIM, true>
+                        : dense_collect_merge_qmask_kernel<DIM, false>;
+    if (int rc = allow_lds(kern, kColMergeLds)) return rc;
+    kern<<<grid, dim3(kDenseMergeThreads), kColMergeLds, stream>>>(
         w.col_cnt, w.col_list, kCollectCap, w.help_done, nq, idx->rows, idx->inv_norm, idx->norm2,
         f.mask, f.qm.stride, f.qm.q_mask, f.qm.n_masks, idx->n_rows, queries, w.inv_q, k,
         idx->ordinal_base, out_scores, out_ids, out_rank, out_count, out_flags, ARMI_FLAG_QMASK);
@@ -2894,7 +2904,7 @@ int dense_topk_impl(const armi_index* idx, const uint16_t* queries, int nq, int 
   const void* img = nullptr;
   if (qmask) {
     const int rc_l = armi::timed_kernel(
-        ARMI_TIMING_QMASK_PREP, qmask_prep_kernel,
+        ARMI_TIMING_QMASK_PREP, f.table ? qmask_prep_kernel<true> : qmask_prep_kernel<false>,
         dim3((unsigned)((T + kPrepTiles - 1) / kPrepTiles), sp.n_qb * (kQB / kPrepQueries)),
         dim3(256), 0, stream, f.mask, f.qm.stride, f.qm.q_mask, f.qm.n_masks, nq, idx->n_rows, T,
         idx->perm_mul, static_cast<uint32_t*>(f.img));
@@ -3632,6 +3642,34 @@ int armi_dense_topk_qmask(const armi_index* idx, const uint16_t* queries, int n_
                "armi_dense_topk_qmask: workspace too small");
   const QMask qm{q_mask, mask_stride_words, n_masks, n_queries};
   return dense_topk_checked(idx, queries, n_queries, k, DenseFilter{row_masks, qm, nullptr},
+                            out_scores, out_ids, out_rank, out_count, out_flags, workspace, stream);
+}
+
+// The same call with the masks named by a device table of pointers (one allocation per mask)
+// instead of a stack: only qmask_prep_kernel and the collect merge's helpers read the caller's
+// masks, and they run their table instances (DenseFilter::table).
+int armi_dense_topk_qmask_ptrs(const armi_index* idx, const uint16_t* queries, int n_queries, int k,
+                               const uint64_t* const* mask_ptrs, const int32_t* q_mask,
+                               int n_masks, float* out_scores, int64_t* out_ids, double* out_rank,
+                               int32_t* out_count, uint32_t* out_flags, void* workspace,
+                               size_t workspace_bytes, hipStream_t stream) {
+  ARMI_REQUIRE(idx != nullptr, "armi_dense_topk_qmask_ptrs: index is null");
+  ARMI_REQUIRE(n_queries >= 0, "armi_dense_topk_qmask_ptrs: n_queries < 0");
+  ARMI_REQUIRE(k >= 1 && k <= kMaxK, "armi_dense_topk_qmask_ptrs: k must be in [1, 240]");
+  ARMI_REQUIRE(n_masks >= 0, "armi_dense_topk_qmask_ptrs: n_masks < 0");
+  if (n_queries == 0) return ARMI_OK;
+  if (!qmask_supported(idx, n_queries, k))
+    return armi::fail(
+        ARMI_ERR_UNSUPPORTED,
+        "armi_dense_topk_qmask_ptrs: needs an int8 image, n_queries <= 128 and k <= 64");
+  ARMI_REQUIRE(queries && q_mask && (mask_ptrs || n_masks == 0) && out_scores && out_ids &&
+                   out_count && out_flags && workspace,
+               "armi_dense_topk_qmask_ptrs: null pointer argument");
+  ARMI_REQUIRE(workspace_bytes >= armi_dense_qmask_workspace_bytes(idx, n_queries, k, n_masks),
+               "armi_dense_topk_qmask_ptrs: workspace too small");
+  const QMask qm{q_mask, 0, n_masks, n_queries};
+  return dense_topk_checked(idx, queries, n_queries, k,
+                            DenseFilter{armi::qmask_table(mask_ptrs), qm, nullptr, true},
                             out_scores, out_ids, out_rank, out_count, out_flags, workspace, stream);
 }
 

@@ -685,7 +685,9 @@ __device__ __forceinline__ int2 range_cursor(int32_t t, int g, int64_t lo, int n
 // kQM = true (the *_qmask_kernel instances): row_mask is the caller's [n_masks][stride] stack and
 // query q of the pass is filtered by its own row of it (qm, see QMask); the words of the wave's
 // four queries are loaded where the shared word is, and candidates() tests each query's own bits.
-template <bool kCollect, bool kQM>
+// kTable (armi_sparse_topk_qmask_ptrs): row_mask carries the call's table of mask pointers instead
+// of the stack (qmask_row<kTable>, resolved once per wave and query, in front of the step loop).
+template <bool kCollect, bool kQM, bool kTable = false>
 __device__ __forceinline__ void sparse_scan_body(
     const int32_t* __restrict__ term_ptr, const int2* __restrict__ post,
     const int32_t* __restrict__ long_of,
@@ -1028,7 +1030,7 @@ __device__ __forceinline__ void sparse_scan_body(
   // the mask rows of the wave's four queries (null: unfiltered)
   const uint64_t* mrow[kMW];
 #pragma unroll
-  for (int j = 0; j < kMW; ++j) mrow[j] = kQM ? qmask_row(row_mask, qm, qw[j]) : nullptr;
+  for (int j = 0; j < kMW; ++j) mrow[j] = kQM ? qmask_row<kTable>(row_mask, qm, qw[j]) : nullptr;
   unsigned long long tp[6] = {0, 0, 0, 0, 0, 0};
   unsigned long long t_a = 0, t_b = 0;
   (void)tp;
@@ -1191,8 +1193,8 @@ __global__ __launch_bounds__(kScanThreads) void sparse_scan_kernel(
                                     coll_row, dbg, dense_of, dense_val, dense_stride, done_flags);
 }
 
-// the per-query-mask sibling (armi_sparse_topk_qmask)
-template <bool kCollect>
+// the per-query-mask siblings (armi_sparse_topk_qmask; kTable: armi_sparse_topk_qmask_ptrs)
+template <bool kCollect, bool kTable>
 __global__ __launch_bounds__(kScanThreads) void sparse_scan_qmask_kernel(
     const int32_t* __restrict__ term_ptr, const int2* __restrict__ post,
     const int32_t* __restrict__ long_of,
@@ -1207,7 +1209,7 @@ __global__ __launch_bounds__(kScanThreads) void sparse_scan_qmask_kernel(
     int32_t* __restrict__ coll_row, int dbg, const int32_t* __restrict__ dense_of,
     const uint32_t* __restrict__ dense_val, int64_t dense_stride,
     const uint32_t* __restrict__ done_flags) {
-  sparse_scan_body<kCollect, true>(term_ptr, post, long_of, start_tab, n_rows, range_rows, n_ranges,
+  sparse_scan_body<kCollect, true, kTable>(term_ptr, post, long_of, start_tab, n_rows, range_rows, n_ranges,
                                    row_masks, qm, nq, uterm, n_terms, ql, qu, qcount, qof, cursors,
                                    cand_key, cand_row, cand_bound, thr, coll_count, coll_key,
                                    coll_row, dbg, dense_of, dense_val, dense_stride, done_flags);
@@ -1390,8 +1392,9 @@ constexpr size_t kCollectLds =
 
 // kQM = true (sparse_collect_merge_qmask_kernel): the helpers test a row against the query's own
 // row of the mask stack, and every query's flags leave with ARMI_FLAG_QMASK set (this is the
-// pass's last kernel, and the only writer of a query's flags at that point).
-template <bool kQM>
+// pass's last kernel, and the only writer of a query's flags at that point). kTable: row_mask
+// carries the call's table of mask pointers (armi_sparse_topk_qmask_ptrs).
+template <bool kQM, bool kTable = false>
 __device__ __forceinline__ void sparse_collect_merge_body(
     const int* __restrict__ coll_count, float* __restrict__ coll_key,
     int32_t* __restrict__ coll_row, int* __restrict__ help_done, int nq, int q_first, int k,
@@ -1476,7 +1479,7 @@ __device__ __forceinline__ void sparse_collect_merge_body(
     const int slot = sh[0];
     const int nt = qcount[slot];
     // kQM: the query's own mask row (uniform; null: unfiltered)
-    const uint64_t* __restrict__ qrow = kQM ? qmask_row(row_mask, qm, ql) : nullptr;
+    const uint64_t* __restrict__ qrow = kQM ? qmask_row<kTable>(row_mask, qm, ql) : nullptr;
     for (int j = tid; j < nt; j += 256) {  // the query's terms, ascending
       const int32_t t = uterm[qu[slot * kQStride + j]];
       tw[j] = qlist[slot * kQStride + j].w;
@@ -1626,6 +1629,7 @@ __global__ __launch_bounds__(256) void sparse_collect_merge_kernel(
                                    out_scores, out_ids, out_count, flags);
 }
 
+template <bool kTable>
 __global__ __launch_bounds__(256) void sparse_collect_merge_qmask_kernel(
     const int* __restrict__ coll_count, float* __restrict__ coll_key,
     int32_t* __restrict__ coll_row, int* __restrict__ help_done, int nq, int q_first, int k,
@@ -1636,7 +1640,7 @@ __global__ __launch_bounds__(256) void sparse_collect_merge_qmask_kernel(
     const int32_t* __restrict__ qu, const int32_t* __restrict__ qcount,
     const int32_t* __restrict__ qof, float* __restrict__ out_scores,
     int64_t* __restrict__ out_ids, int32_t* __restrict__ out_count, uint32_t* __restrict__ flags) {
-  sparse_collect_merge_body<true>(coll_count, coll_key, coll_row, help_done, nq, q_first, k,
+  sparse_collect_merge_body<true, kTable>(coll_count, coll_key, coll_row, help_done, nq, q_first, k,
                                    ordinal_base, n_rows, row_masks, qm, term_ptr, post, dense_of,
                                    dense_val, dense_stride, uterm, qlist, qu, qcount, qof,
                                    out_scores, out_ids, out_count, flags);
@@ -2645,15 +2649,27 @@ namespace {
 // The launch sequence of armi_sparse_topk and armi_sparse_topk_qmask (arguments checked by the
 // entry points). q_mask == nullptr: row_mask is the call's one shared mask (or null). q_mask set:
 // row_mask is the [n_masks][mask_stride] stack and every kernel that tests a mask runs its
-// per-query sibling; the pass offset q0 reaches the kernels as q_mask + q0.
+// per-query sibling; the pass offset q0 reaches the kernels as q_mask + q0. table
+// (armi_sparse_topk_qmask_ptrs): row_mask carries the table of n_masks mask pointers instead
+// (armi::qmask_table) and the siblings run their table instances.
 int sparse_topk_launch(const armi_sparse_index* idx, const int32_t* q_indptr,
                        const int32_t* q_indices, const float* q_values, int n_queries, int k,
                        const uint64_t* row_mask, int64_t mask_stride, const int32_t* q_mask,
                        int n_masks, float* out_scores, int64_t* out_ids, int32_t* out_count,
-                       uint32_t* out_flags, void* workspace, hipStream_t stream) {
+                       uint32_t* out_flags, void* workspace, hipStream_t stream,
+                       bool table = false) {
   const bool qmask = q_mask != nullptr;
   ARMI_HIP(hipSetDevice(idx->device));
   const Workspace w = carve(workspace, idx);
+  // the per-query-mask kernels of the call's mask form
+  const auto scan_qm = table ? sparse_scan_qmask_kernel<false, true>
+                             : sparse_scan_qmask_kernel<false, false>;
+  const auto collect_qm = table ? sparse_scan_qmask_kernel<true, true>
+                                : sparse_scan_qmask_kernel<true, false>;
+  const auto collect_merge_qm = table ? sparse_collect_merge_qmask_kernel<true>
+                                      : sparse_collect_merge_qmask_kernel<false>;
+  const auto filter_qm = table ? sparse_filter_scan_qmask_kernel<true>
+                               : sparse_filter_scan_qmask_kernel<false>;
 #ifdef ARMI_SPARSE_PROFILE
   static const int dbg = getenv("ARMI_SPARSE_DBG") ? atoi(getenv("ARMI_SPARSE_DBG")) : 0;
 #else
@@ -2668,10 +2684,10 @@ int sparse_topk_launch(const armi_sparse_index* idx, const int32_t* q_indptr,
   if (int rc = armi::allow_lds(sparse_scan_kernel<true>, kScanLds)) return rc;
   if (int rc = armi::allow_lds(sparse_filter_scan_kernel, kFLds)) return rc;
   if (qmask) {
-    if (int rc = armi::allow_lds(sparse_collect_merge_qmask_kernel, kCollectLds)) return rc;
-    if (int rc = armi::allow_lds(sparse_scan_qmask_kernel<false>, kScanLds)) return rc;
-    if (int rc = armi::allow_lds(sparse_scan_qmask_kernel<true>, kScanLds)) return rc;
-    if (int rc = armi::allow_lds(sparse_filter_scan_qmask_kernel, kFLds)) return rc;
+    if (int rc = armi::allow_lds(collect_merge_qm, kCollectLds)) return rc;
+    if (int rc = armi::allow_lds(scan_qm, kScanLds)) return rc;
+    if (int rc = armi::allow_lds(collect_qm, kScanLds)) return rc;
+    if (int rc = armi::allow_lds(filter_qm, kFLds)) return rc;
   }
   const int n_help = std::max(1, std::min(kMaxHelp, kCollectCap / k));
   // the MFMA filter answers what it can certify; kc = the rescored candidates per query
@@ -2709,7 +2725,7 @@ int sparse_topk_launch(const armi_sparse_index* idx, const int32_t* q_indptr,
     if (filter) {
       const int rc_f =
           qmask ? armi::timed_kernel(
-                      scan_slot, sparse_filter_scan_qmask_kernel, dim3(idx->n_ranges),
+                      scan_slot, filter_qm, dim3(idx->n_ranges),
                       dim3(kFThreads), kFLds, stream, (const int32_t*)idx->term_ptr,
                       reinterpret_cast<const int2*>(idx->post), (const int32_t*)idx->long_of,
                       (const int32_t*)idx->start_tab, idx->n_rows, idx->range_rows, idx->n_ranges,
@@ -2788,7 +2804,7 @@ int sparse_topk_launch(const armi_sparse_index* idx, const int32_t* q_indptr,
     armi::TimedLaunch tl;
     if (!filter && tl.begin(scan_slot, stream) < 0) return ARMI_ERR_HIP;
     if (qmask)
-      sparse_scan_qmask_kernel<false><<<dim3(idx->n_ranges), dim3(kScanThreads), kScanLds, stream>>>(
+      scan_qm<<<dim3(idx->n_ranges), dim3(kScanThreads), kScanLds, stream>>>(
           idx->term_ptr, reinterpret_cast<const int2*>(idx->post), idx->long_of, idx->start_tab,
           idx->n_rows, idx->range_rows, idx->n_ranges, row_mask, qm, nqp, w.uterm, w.n_terms, w.ql,
           w.qu, w.qcount, w.qof, w.cursors, w.cand_key, w.cand_row, w.cand_bound, nullptr, nullptr,
@@ -2838,7 +2854,7 @@ int sparse_topk_launch(const armi_sparse_index* idx, const int32_t* q_indptr,
         out_scores, out_ids, out_count, pflags, w.kth);
     ARMI_LAUNCHED("sparse_merge_kernel");
     if (qmask)
-      sparse_scan_qmask_kernel<true><<<dim3(idx->n_ranges), dim3(kScanThreads), kScanLds, stream>>>(
+      collect_qm<<<dim3(idx->n_ranges), dim3(kScanThreads), kScanLds, stream>>>(
           idx->term_ptr, reinterpret_cast<const int2*>(idx->post), idx->long_of, idx->start_tab,
           idx->n_rows, idx->range_rows, idx->n_ranges, row_mask, qm, nqp, w.uterm, w.n_terms, w.ql,
           w.qu, w.qcount, w.qof, w.cursors, nullptr, nullptr, nullptr, w.kth, w.coll_count,
@@ -2851,7 +2867,7 @@ int sparse_topk_launch(const armi_sparse_index* idx, const int32_t* q_indptr,
         idx->dense_of, idx->dense_val, idx->dense_stride, nullptr);
     ARMI_LAUNCHED("sparse_collect_kernel");
     if (qmask)
-      sparse_collect_merge_qmask_kernel<<<dim3(nqp + n_help), dim3(256), kCollectLds, stream>>>(
+      collect_merge_qm<<<dim3(nqp + n_help), dim3(256), kCollectLds, stream>>>(
           w.coll_count, w.coll_key, w.coll_row, w.coll_count + kQB, nqp, q0, k, idx->ordinal_base,
           idx->n_rows, row_mask, qm, idx->term_ptr, reinterpret_cast<const int2*>(idx->post),
           idx->dense_of, idx->dense_val, idx->dense_stride, w.uterm, w.ql, w.qu, w.qcount, w.qof,
@@ -2912,6 +2928,27 @@ int armi_sparse_topk_qmask(const armi_sparse_index* idx, const int32_t* q_indptr
   return sparse_topk_launch(idx, q_indptr, q_indices, q_values, n_queries, k, row_masks,
                             mask_stride_words, q_mask, n_masks, out_scores, out_ids, out_count,
                             out_flags, workspace, stream);
+}
+
+// The same call with the masks named by a device table of pointers (one allocation per mask).
+int armi_sparse_topk_qmask_ptrs(const armi_sparse_index* idx, const int32_t* q_indptr,
+                                const int32_t* q_indices, const float* q_values, int n_queries,
+                                int k, const uint64_t* const* mask_ptrs, const int32_t* q_mask,
+                                int n_masks, float* out_scores, int64_t* out_ids,
+                                int32_t* out_count, uint32_t* out_flags, void* workspace,
+                                size_t workspace_bytes, hipStream_t stream) {
+  ARMI_REQUIRE(n_masks >= 0, "armi_sparse_topk_qmask_ptrs: n_masks < 0");
+  ARMI_REQUIRE(idx != nullptr, "armi_sparse_topk_qmask_ptrs: index is null");
+  ARMI_REQUIRE(k >= 1 && k <= kMaxK, "armi_sparse_topk_qmask_ptrs: k must be in [1, 240]");
+  if (n_queries <= 0) return ARMI_OK;
+  ARMI_REQUIRE(q_indptr && q_indices && q_values && q_mask && (mask_ptrs || n_masks == 0) &&
+                   out_scores && out_ids && out_count && out_flags && workspace,
+               "armi_sparse_topk_qmask_ptrs: null pointer argument");
+  ARMI_REQUIRE(workspace_bytes >= armi_sparse_workspace_bytes(idx, n_queries, k),
+               "armi_sparse_topk_qmask_ptrs: workspace too small");
+  return sparse_topk_launch(idx, q_indptr, q_indices, q_values, n_queries, k,
+                            armi::qmask_table(mask_ptrs), 0, q_mask, n_masks, out_scores, out_ids,
+                            out_count, out_flags, workspace, stream, /*table=*/true);
 }
 
 int armi_sparse_index_set_filter(armi_sparse_index* index, int enable, int* usable) {

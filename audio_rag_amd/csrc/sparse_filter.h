@@ -450,7 +450,10 @@ __device__ __forceinline__ void filter_prep_block(int nU, const QTerm* __restric
 // step loop spilled (100 to 350 B of scratch per lane); instead every tile runs one path in which
 // a score is ANDed with its row's sign-extended bit (two VALU per score, no select), which for an
 // unfiltered pass is the range test alone. DESIGN.md section 15 has the measured cost.
-template <bool kQM>
+// kTable (armi_sparse_topk_qmask_ptrs): row_mask carries the call's table of mask pointers; the
+// lane fetches its column's entry where the stack form computes its row (per tile, with the mask
+// index; a null entry is an unfiltered column).
+template <bool kQM, bool kTable = false>
 __device__ __forceinline__ void sparse_filter_scan_body(
     const int32_t* __restrict__ term_ptr, const int2* __restrict__ post,
     const int32_t* __restrict__ long_of, const int32_t* __restrict__ start_tab, int64_t n_rows,
@@ -697,8 +700,16 @@ __device__ __forceinline__ void sparse_filter_scan_body(
       for (int h = 0; h < 2; ++h) {
         __builtin_amdgcn_sched_barrier(0);
         const int32_t mq = any_mask ? armi::qmask_index(qm, 32 * h + (lane & 31)) : -1;
-        const uint32_t* mrow32 =
-            reinterpret_cast<const uint32_t*>(row_mask + (size_t)max(mq, 0) * qm.stride);
+        bool masked = mq >= 0;
+        const uint32_t* mrow32;
+        if constexpr (kTable) {  // (no entry is read for an unfiltered column: the table may be null)
+          mrow32 = reinterpret_cast<const uint32_t*>(
+              masked ? armi::qmask_row_of<true>(row_mask, qm, mq) : nullptr);
+          masked = mrow32 != nullptr;
+        } else {
+          mrow32 = reinterpret_cast<const uint32_t*>(
+              armi::qmask_row_of<false>(row_mask, qm, max(mq, 0)));
+        }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int32_t rb = tlo + 32 * (4 * wave + i);  // a multiple of 32
@@ -706,7 +717,7 @@ __device__ __forceinline__ void sparse_filter_scan_body(
           // half rb / 32 of its mask row), shifted to the lane's rows
           const int32_t left = thi - rb;  // uniform
           uint32_t mb = left >= 32 ? 0xffffffffu : (left > 0 ? (1u << left) - 1u : 0u);
-          if (mq >= 0 && left > 0) mb &= mrow32[rb >> 5];
+          if (masked && left > 0) mb &= mrow32[rb >> 5];
           mb >>= 4 * (lane >> 5);
           // a cleared bit zeroes the score (every score is >= +0) by an AND with the sign-extended
           // bit, not by a select: the selects' lane masks did not fit the scalar registers
@@ -858,6 +869,7 @@ __global__ __launch_bounds__(kFThreads) void sparse_filter_scan_kernel(
                                  term_scale, fB, fscale, cand_key, cand_row, cand_bound);
 }
 
+template <bool kTable>
 __global__ __launch_bounds__(kFThreads) void sparse_filter_scan_qmask_kernel(
     const int32_t* __restrict__ term_ptr, const int2* __restrict__ post,
     const int32_t* __restrict__ long_of, const int32_t* __restrict__ start_tab, int64_t n_rows,
@@ -867,7 +879,7 @@ __global__ __launch_bounds__(kFThreads) void sparse_filter_scan_qmask_kernel(
     const float* __restrict__ term_scale, const uint16_t* __restrict__ fB,
     const float* __restrict__ fscale, float* __restrict__ cand_key,
     int32_t* __restrict__ cand_row, float* __restrict__ cand_bound) {
-  sparse_filter_scan_body<true>(term_ptr, post, long_of, start_tab, n_rows, range_rows, n_ranges,
+  sparse_filter_scan_body<true, kTable>(term_ptr, post, long_of, start_tab, n_rows, range_rows, n_ranges,
                                  row_masks, qm, uterm, n_terms, col8_of, dense_u8, stride8,
                                  term_scale, fB, fscale, cand_key, cand_row, cand_bound);
 }

@@ -24,6 +24,12 @@
 // batch's sparse top-2k list, which is the sparse top-k: one ranking, (score desc, id asc)) and
 // the payload filter (a device row bitmask per batch: a query with another mask seals the
 // collecting batch, which the dispatcher then hands over at once).
+// A server created with ARMI_STREAM_QUERY_MASKS (armi_stream_create_ex) keeps one filter per
+// request inside one coalesced batch instead: no query seals a batch, each slot keeps its queries'
+// mask pointers, a batch whose queries all carry one pointer runs the calls above verbatim, and a
+// mixed batch takes its lists from armi_dense_topk_qmask_ptrs (in calls of at most kQMaskCall
+// queries) and armi_sparse_topk_qmask_ptrs, which read the masks in place through the slot's
+// pointer table: nothing is stacked or copied but max_batch pointers and int32 per batch.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -48,6 +54,7 @@ inline int64_t now_ns() {
 
 constexpr int kSlots = 3;           // batches in flight (GPU running / collected / collecting)
 constexpr int kMaxTerms = 256;      // sparse terms per query (armi_sparse_topk's limit)
+constexpr int kQMaskCall = 128;     // queries per armi_dense_topk_qmask_ptrs call (its limit)
 // Result ring entries (tickets whose results stay readable): the largest power of two whose
 // payload fits 128 MiB of host memory (2^19 tickets at k = 10), at least 2^14 and 64 * max_batch.
 // A caller that lets a ticket fall a whole ring behind gets "result overwritten" from
@@ -81,6 +88,13 @@ struct Slot {
   std::vector<int32_t> qmode;        // [max_batch] branch (0 dense, 1 hybrid, 2 sparse)
   const uint64_t* mask = nullptr;    // the batch's row filter (every query of the batch)
   bool sealed = false;               // closed early: the next query needs another mask
+  // ARMI_STREAM_QUERY_MASKS servers: every query's mask (mask = the first query's), and whether
+  // two of them differ (the batch then runs the *_qmask_ptrs calls)
+  bool mixed = false;
+  const uint64_t** h_masks = nullptr;  // pinned [max_batch]
+  const uint64_t** d_masks = nullptr;
+  int32_t* h_qmask = nullptr;          // pinned [max_batch]: i, or -1 for a null mask
+  int32_t* d_qmask = nullptr;
   // hybrid servers: the batch's sparse query CSR (pinned + device), prefetch lists, fusion
   int nnz = 0;
   int32_t* h_sp_ptr = nullptr;       // [max_batch + 1]
@@ -150,6 +164,8 @@ struct armi_stream {
   int64_t next_ticket = 0;
   bool stop = false;
   std::atomic<int64_t> batches{0}, queries{0};
+  bool query_masks = false;              // ARMI_STREAM_QUERY_MASKS
+  std::atomic<int64_t> mixed_batches{0};  // batches answered through the *_qmask_ptrs calls
   std::thread dispatcher, completer;
   int device = 0;
   int64_t ring_n = 0;                    // ring entries (a power of two)
@@ -161,8 +177,26 @@ namespace {
 int launch_slot(armi_stream* s, Slot& sl) {
   const size_t qbytes = (size_t)sl.n * s->dim * sizeof(uint16_t);
   ARMI_HIP(hipMemcpyAsync(sl.d_queries, sl.h_queries, qbytes, hipMemcpyHostToDevice, s->stream));
-  int rc = armi_dense_topk(s->idx, sl.d_queries, sl.n, s->kp, sl.mask, sl.d_scores, sl.d_ids,
-                           sl.d_rank, sl.d_count, sl.d_flags, sl.d_ws, s->ws_bytes, s->stream);
+  int rc = ARMI_OK;
+  if (sl.mixed) {
+    // the batch's mask table and q_mask, then the dense list in calls of at most kQMaskCall
+    // queries on the one stream and workspace (q_mask numbers the whole batch's table)
+    ARMI_HIP(hipMemcpyAsync(sl.d_masks, sl.h_masks, (size_t)sl.n * sizeof(uint64_t*),
+                            hipMemcpyHostToDevice, s->stream));
+    ARMI_HIP(hipMemcpyAsync(sl.d_qmask, sl.h_qmask, (size_t)sl.n * sizeof(int32_t),
+                            hipMemcpyHostToDevice, s->stream));
+    for (int q0 = 0; q0 < sl.n && rc == ARMI_OK; q0 += kQMaskCall) {
+      const int nc = std::min(kQMaskCall, sl.n - q0);
+      const size_t o = (size_t)q0 * s->kp;
+      rc = armi_dense_topk_qmask_ptrs(s->idx, sl.d_queries + (size_t)q0 * s->dim, nc, s->kp,
+                                      sl.d_masks, sl.d_qmask + q0, sl.n, sl.d_scores + o,
+                                      sl.d_ids + o, sl.d_rank + o, sl.d_count + q0,
+                                      sl.d_flags + q0, sl.d_ws, s->ws_bytes, s->stream);
+    }
+  } else {
+    rc = armi_dense_topk(s->idx, sl.d_queries, sl.n, s->kp, sl.mask, sl.d_scores, sl.d_ids,
+                         sl.d_rank, sl.d_count, sl.d_flags, sl.d_ws, s->ws_bytes, s->stream);
+  }
   if (rc != ARMI_OK) return rc;
   if (s->sidx && sl.nnz > 0) {  // (no query of the batch has terms: every answer is dense)
     ARMI_HIP(hipMemcpyAsync(sl.d_sp_ptr, sl.h_sp_ptr, (size_t)(sl.n + 1) * sizeof(int32_t),
@@ -173,9 +207,15 @@ int launch_slot(armi_stream* s, Slot& sl) {
       ARMI_HIP(hipMemcpyAsync(sl.d_sp_val, sl.h_sp_val, (size_t)sl.nnz * sizeof(float),
                               hipMemcpyHostToDevice, s->stream));
     }
-    rc = armi_sparse_topk(s->sidx, sl.d_sp_ptr, sl.d_sp_idx, sl.d_sp_val, sl.n, s->kp, sl.mask,
-                          sl.d_sp_scores, sl.d_sp_ids, sl.d_sp_count, sl.d_sp_flags, sl.d_sp_ws,
-                          s->sws_bytes, s->stream);
+    if (sl.mixed)
+      rc = armi_sparse_topk_qmask_ptrs(s->sidx, sl.d_sp_ptr, sl.d_sp_idx, sl.d_sp_val, sl.n, s->kp,
+                                       sl.d_masks, sl.d_qmask, sl.n, sl.d_sp_scores, sl.d_sp_ids,
+                                       sl.d_sp_count, sl.d_sp_flags, sl.d_sp_ws, s->sws_bytes,
+                                       s->stream);
+    else
+      rc = armi_sparse_topk(s->sidx, sl.d_sp_ptr, sl.d_sp_idx, sl.d_sp_val, sl.n, s->kp, sl.mask,
+                            sl.d_sp_scores, sl.d_sp_ids, sl.d_sp_count, sl.d_sp_flags, sl.d_sp_ws,
+                            s->sws_bytes, s->stream);
     if (rc != ARMI_OK) return rc;
     rc = armi_rrf_fuse(sl.d_ids, sl.d_count, s->kp, sl.d_sp_ids, sl.d_sp_count, s->kp, sl.n,
                        s->rrf_k, s->k, sl.d_f_ids, sl.d_f_score, sl.d_f_count, s->stream);
@@ -255,6 +295,11 @@ void completer_main(armi_stream* s) {
     int status = sl.status;
     if (status == ARMI_OK && hipEventSynchronize(sl.done) != hipSuccess) status = ARMI_ERR_HIP;
     const int64_t t = now_ns();
+    // (counted before the batch's results are published: a caller whose wait has returned finds
+    // its batch in the statistics)
+    s->batches.fetch_add(1);
+    s->queries.fetch_add(sl.n);
+    if (sl.mixed) s->mixed_batches.fetch_add(1);
     for (int i = 0; i < sl.n; ++i) {
       const int64_t tk = sl.first_ticket + i;
       Entry& e = s->ring[tk % s->ring_n];
@@ -312,10 +357,9 @@ void completer_main(armi_stream* s) {
       e.t_done = t;
       e.ticket.store(tk, std::memory_order_release);
     }
-    s->batches.fetch_add(1);
-    s->queries.fetch_add(sl.n);
     lk.lock();
     sl.n = 0;
+    sl.mixed = false;
     sl.nnz = 0;
     sl.mask = nullptr;
     sl.sealed = false;
@@ -334,13 +378,14 @@ void free_slot(Slot& sl) {
   if (sl.h_count) (void)hipHostFree(sl.h_count);
   for (void* p : {(void*)sl.h_sp_ptr, (void*)sl.h_sp_idx, (void*)sl.h_sp_val, (void*)sl.h_f_ids,
                   (void*)sl.h_f_score, (void*)sl.h_f_count, (void*)sl.h_sp_scores,
-                  (void*)sl.h_sp_ids, (void*)sl.h_sp_count})
+                  (void*)sl.h_sp_ids, (void*)sl.h_sp_count, (void*)sl.h_masks, (void*)sl.h_qmask})
     if (p) (void)hipHostFree(p);
   for (void* p : {(void*)sl.d_queries, (void*)sl.d_scores, (void*)sl.d_ids, (void*)sl.d_rank,
                   (void*)sl.d_count, (void*)sl.d_flags, sl.d_ws, (void*)sl.d_sp_ptr,
                   (void*)sl.d_sp_idx, (void*)sl.d_sp_val, (void*)sl.d_sp_scores,
                   (void*)sl.d_sp_ids, (void*)sl.d_sp_count, (void*)sl.d_sp_flags, sl.d_sp_ws,
-                  (void*)sl.d_f_ids, (void*)sl.d_f_score, (void*)sl.d_f_count})
+                  (void*)sl.d_f_ids, (void*)sl.d_f_score, (void*)sl.d_f_count, (void*)sl.d_masks,
+                  (void*)sl.d_qmask})
     if (p) (void)hipFree(p);
   if (sl.done) (void)hipEventDestroy(sl.done);
   sl = Slot{};
@@ -383,6 +428,12 @@ int alloc_slot(armi_stream* s, Slot& sl) {
   ARMI_HIP(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
   sl.t_submit.assign(nq, 0);
   sl.qmode.assign(nq, 0);
+  if (s->query_masks) {
+    ARMI_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_masks), nq * sizeof(uint64_t*)));
+    ARMI_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_qmask), nq * sizeof(int32_t)));
+    ARMI_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_masks), nq * sizeof(uint64_t*)));
+    ARMI_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_qmask), nq * sizeof(int32_t)));
+  }
   if (s->sidx) {
     const size_t nt = nq * kMaxTerms, nf = nq * s->k;
     ARMI_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_sp_ptr), (nq + 1) * sizeof(int32_t)));
@@ -415,13 +466,21 @@ int alloc_slot(armi_stream* s, Slot& sl) {
 namespace {
 
 int create_impl(const armi_index* idx, const armi_sparse_index* sidx, int k, int rrf_k,
-                int max_batch, double max_wait_us, armi_stream** out) {
+                int max_batch, double max_wait_us, unsigned flags, armi_stream** out) {
   ARMI_REQUIRE(idx && out, "armi_stream_create: null pointer argument");
   ARMI_REQUIRE(k >= 1 && k <= (sidx ? 120 : 240), "armi_stream_create: k out of range");
   ARMI_REQUIRE(max_batch >= 1 && max_batch <= 4096, "armi_stream_create: max_batch in [1, 4096]");
   ARMI_REQUIRE(max_wait_us >= 0.0, "armi_stream_create: max_wait_us < 0");
   ARMI_REQUIRE(rrf_k >= 1, "armi_stream_create: rrf_k must be >= 1");
+  ARMI_REQUIRE((flags & ~ARMI_STREAM_QUERY_MASKS) == 0u, "armi_stream_create_ex: unknown flag");
   *out = nullptr;
+  const bool query_masks = (flags & ARMI_STREAM_QUERY_MASKS) != 0u;
+  const int nq_call = std::min(max_batch, kQMaskCall);
+  if (query_masks && !armi_dense_qmask_supported(idx, nq_call, sidx ? 2 * k : k))
+    return armi::fail(ARMI_ERR_UNSUPPORTED,
+                      "armi_stream_create_ex: ARMI_STREAM_QUERY_MASKS needs an index with an int8 "
+                      "image and a dense list of at most 64 (k <= 64 on a dense server, k <= 32 on "
+                      "a hybrid one)");
   auto* s = new armi_stream();
   s->idx = idx;
   s->sidx = sidx;
@@ -432,7 +491,11 @@ int create_impl(const armi_index* idx, const armi_sparse_index* sidx, int k, int
   s->dim = armi_index_dim(idx);
   s->max_wait_ns = (int64_t)(max_wait_us * 1e3);
   s->device = idx->device;
+  s->query_masks = query_masks;
   s->ws_bytes = armi_dense_workspace_bytes(idx, max_batch, s->kp);
+  if (query_masks)
+    s->ws_bytes = std::max(s->ws_bytes,
+                           armi_dense_qmask_workspace_bytes(idx, nq_call, s->kp, nq_call));
   if (sidx) s->sws_bytes = armi_sparse_workspace_bytes(sidx, max_batch, s->kp);
   s->ring_n = ring_entries(max_batch, k);
   s->ring = std::vector<Entry>(s->ring_n);
@@ -495,7 +558,8 @@ int submit_impl(armi_stream* s, const uint16_t* query, const int32_t* sp_idx,
   for (;;) {
     if (s->stop) return armi::fail(ARMI_ERR_INVALID, "armi_stream_submit: server stopped");
     Slot& c = s->slots[s->collect];
-    if (c.n > 0 && !c.sealed && c.mask != mask) {  // another filter: close the collecting batch
+    // another filter: close the collecting batch (a query-masks server keeps collecting)
+    if (!s->query_masks && c.n > 0 && !c.sealed && c.mask != mask) {
       c.sealed = true;
       s->cv_dispatch.notify_one();
     }
@@ -517,6 +581,11 @@ int submit_impl(armi_stream* s, const uint16_t* query, const int32_t* sp_idx,
     }
     c.nnz += nnz;
     c.h_sp_ptr[c.n + 1] = c.nnz;
+  }
+  if (s->query_masks) {
+    c.h_masks[c.n] = mask;
+    c.h_qmask[c.n] = mask ? c.n : -1;
+    c.mixed |= mask != c.mask;
   }
   c.qmode[c.n] = qm;
   c.t_submit[c.n] = now_ns();
@@ -577,13 +646,18 @@ extern "C" {
 
 int armi_stream_create(const armi_index* idx, int k, int max_batch, double max_wait_us,
                        armi_stream** out) {
-  return create_impl(idx, nullptr, k, 2, max_batch, max_wait_us, out);
+  return create_impl(idx, nullptr, k, 2, max_batch, max_wait_us, 0u, out);
 }
 
 int armi_stream_create_hybrid(const armi_index* idx, const armi_sparse_index* sidx, int k,
                               int rrf_k, int max_batch, double max_wait_us, armi_stream** out) {
   ARMI_REQUIRE(sidx, "armi_stream_create_hybrid: sparse index is null");
-  return create_impl(idx, sidx, k, rrf_k, max_batch, max_wait_us, out);
+  return create_impl(idx, sidx, k, rrf_k, max_batch, max_wait_us, 0u, out);
+}
+
+int armi_stream_create_ex(const armi_index* idx, const armi_sparse_index* sidx, int k, int rrf_k,
+                          int max_batch, double max_wait_us, unsigned flags, armi_stream** out) {
+  return create_impl(idx, sidx, k, rrf_k, max_batch, max_wait_us, flags, out);
 }
 
 int armi_stream_stop(armi_stream* s) {
@@ -641,13 +715,37 @@ int armi_stream_stats(armi_stream* s, int64_t* batches, int64_t* queries) {
   return ARMI_OK;
 }
 
+int armi_stream_stats_ex(armi_stream* s, int64_t* batches, int64_t* queries,
+                         int64_t* mixed_batches) {
+  ARMI_REQUIRE(s && batches && queries && mixed_batches,
+               "armi_stream_stats_ex: null pointer argument");
+  Active a(s);
+  *batches = s->batches.load();
+  *queries = s->queries.load();
+  *mixed_batches = s->mixed_batches.load();
+  return ARMI_OK;
+}
+
 int armi_stream_loadgen(armi_stream* s, const uint16_t* queries, const int32_t* q_indptr,
                         const int32_t* q_indices, const float* q_values, int64_t n_vectors,
                         int64_t n_queries, double qps, uint64_t seed, double* latency_us,
                         double* elapsed_s, int64_t* completed, int64_t* out_ids,
                         int32_t* out_count) {
+  return armi_stream_loadgen_ex(s, queries, q_indptr, q_indices, q_values, n_vectors, n_queries,
+                                qps, seed, nullptr, 0, latency_us, elapsed_s, completed, out_ids,
+                                out_count);
+}
+
+int armi_stream_loadgen_ex(armi_stream* s, const uint16_t* queries, const int32_t* q_indptr,
+                           const int32_t* q_indices, const float* q_values, int64_t n_vectors,
+                           int64_t n_queries, double qps, uint64_t seed,
+                           const uint64_t* const* masks, int64_t n_masks, double* latency_us,
+                           double* elapsed_s, int64_t* completed, int64_t* out_ids,
+                           int32_t* out_count) {
   ARMI_REQUIRE(s && queries && latency_us && elapsed_s && completed,
                "armi_stream_loadgen: null pointer argument");
+  ARMI_REQUIRE(n_masks >= 0 && (masks || n_masks == 0),
+               "armi_stream_loadgen: n_masks < 0, or masks null with n_masks > 0");
   ARMI_REQUIRE(n_vectors >= 1, "armi_stream_loadgen: n_vectors < 1");
   ARMI_REQUIRE(n_queries >= 1, "armi_stream_loadgen: n_queries < 1");
   ARMI_REQUIRE(qps > 0.0, "armi_stream_loadgen: qps must be > 0");
@@ -694,8 +792,8 @@ int armi_stream_loadgen(armi_stream* s, const uint16_t* queries, const int32_t* 
     const int64_t v = i % n_vectors;
     const int nnz = q_indptr ? q_indptr[v + 1] - q_indptr[v] : 0;
     rc = submit_impl(s, queries + (size_t)v * s->dim, q_indptr ? q_indices + q_indptr[v] : nullptr,
-                     q_indptr ? q_values + q_indptr[v] : nullptr, nnz, ARMI_STREAM_AUTO, nullptr,
-                     &tickets[(size_t)i]);
+                     q_indptr ? q_values + q_indptr[v] : nullptr, nnz, ARMI_STREAM_AUTO,
+                     n_masks > 0 ? masks[i % n_masks] : nullptr, &tickets[(size_t)i]);
     if (rc == ARMI_OK) n_sub.store(i + 1, std::memory_order_release);
   }
   if (rc != ARMI_OK) rc_col.store(rc);  // stops the collector

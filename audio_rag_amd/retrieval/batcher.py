@@ -228,7 +228,14 @@ class StreamServer:
     with terms by the sparse-only branch (qdrant.py:299-311: sparse top-k, hit.score = the dot).
     submit() takes a per-query search_type and filter_metadata as search() does: the filter is
     the collection's device row bitmask (ChunkCollection.filter_mask), held by the server until
-    the ticket's result is read; the native server batches queries of one filter together.
+    the ticket's result is read. By default a native batch holds queries of one filter (a query
+    with another filter closes the collecting batch, which leaves at once). query_masks=True
+    (armi_stream_create_ex with ARMI_STREAM_QUERY_MASKS) keeps requests of different filters in
+    one batch instead: a batch leaves when it is full or max_wait_ms old, a batch of one filter
+    runs the same calls as before, and a mixed one is answered by the per-query-mask kernels
+    through a table of the requests' mask pointers, with the same results bit for bit. It needs
+    top_k <= 64 on a dense server and <= 32 on a hybrid / sparse one (the dense list of a call
+    is at most 64) and raises RetrievalError otherwise; stats_ex() counts the mixed batches.
 
     Lifetime: the collection knows its open servers and closes them before it frees its device
     indexes (ChunkCollection.close: delete_collection, load_collection, attach_collection); close()
@@ -236,7 +243,7 @@ class StreamServer:
 
     def __init__(self, retriever: MI355XRetriever, collection_name: str | None = None,
                  top_k: int | None = None, max_batch: int = 64, max_wait_ms: float = 2.0,
-                 search_type: str = "dense"):
+                 search_type: str = "dense", query_masks: bool = False):
         from audio_rag_amd import _armi
 
         if search_type not in ("dense", "hybrid", "sparse"):
@@ -257,7 +264,16 @@ class StreamServer:
         self._inflight = 0
         self._closed = False
         self._masks: dict[int, torch.Tensor] = {}  # ticket -> row filter the batch still reads
-        if self.hybrid:
+        self.query_masks = bool(query_masks)
+        if self.query_masks:
+            try:
+                _armi.call("armi_stream_create_ex", self.index.handle,
+                           self.sparse_index.handle if self.hybrid else None, self.k,
+                           retriever.config.rrf_k, max_batch, float(max_wait_ms) * 1e3,
+                           _armi.ARMI_STREAM_QUERY_MASKS, _armi.ctypes.byref(self._handle))
+            except _armi.ArmiError as e:  # e.g. a top_k the per-query-mask scan does not serve
+                raise RetrievalError(str(e)) from e
+        elif self.hybrid:
             _armi.call("armi_stream_create_hybrid", self.index.handle, self.sparse_index.handle,
                        self.k, retriever.config.rrf_k, max_batch, float(max_wait_ms) * 1e3,
                        _armi.ctypes.byref(self._handle))
@@ -377,11 +393,20 @@ class StreamServer:
         self._call("armi_stream_stats", self._armi.ctypes.byref(b), self._armi.ctypes.byref(q))
         return b.value, q.value
 
+    def stats_ex(self) -> tuple[int, int, int]:
+        """(batches, queries, mixed batches): the last counts the batches that held more than one
+        filter and were answered by the per-query-mask kernels (query_masks=True only)."""
+        b, q, m = (self._armi.ctypes.c_int64() for _ in range(3))
+        self._call("armi_stream_stats_ex", self._armi.ctypes.byref(b),
+                   self._armi.ctypes.byref(q), self._armi.ctypes.byref(m))
+        return b.value, q.value, m.value
+
     def loadgen(self, queries: np.ndarray, n_queries: int, qps: float, seed: int = 0,
                 sparse_csr: tuple[np.ndarray, np.ndarray, np.ndarray] | None = None,
-                answers: bool = False):
-        """Native open-loop Poisson load at `qps` (armi_stream_loadgen): query i = row
-        (i % len(queries)) with, on a hybrid server, the terms of CSR row (i % len(queries)).
+                answers: bool = False, filters: list[dict | None] | None = None):
+        """Native open-loop Poisson load at `qps` (armi_stream_loadgen_ex): query i = row
+        (i % len(queries)) with, on a hybrid server, the terms of CSR row (i % len(queries)),
+        under filters[i % len(filters)] (filter_metadata dicts, None = unfiltered) when given.
         Returns per-query latency in seconds and the elapsed time from the first submit to the
         last completion; with answers=True also every query's ids [n_queries, k] and count."""
         q = np.ascontiguousarray(queries, dtype=np.float16).reshape(-1, self.dim)
@@ -399,8 +424,12 @@ class StreamServer:
             ptrs = tuple(a.ctypes.data for a in keep)
         ids = np.empty((n_queries, self.k), dtype=np.int64) if answers else None
         cnt = np.empty(n_queries, dtype=np.int32) if answers else None
-        self._call("armi_stream_loadgen", q.ctypes.data, *ptrs, q.shape[0], n_queries,
-                   float(qps), seed, lat.ctypes.data, self._armi.ctypes.byref(el),
+        # the filters' device bitmasks, held until the call returns, and their addresses
+        masks = [self.collection.filter_mask(f) for f in (filters or [])]
+        table = np.array([0 if m is None else m.data_ptr() for m in masks], dtype=np.uint64)
+        self._call("armi_stream_loadgen_ex", q.ctypes.data, *ptrs, q.shape[0], n_queries,
+                   float(qps), seed, table.ctypes.data if masks else None, len(masks),
+                   lat.ctypes.data, self._armi.ctypes.byref(el),
                    self._armi.ctypes.byref(done), None if ids is None else ids.ctypes.data,
                    None if cnt is None else cnt.ctypes.data)
         if answers:

@@ -153,6 +153,30 @@ def _check_row_masks(row_masks: torch.Tensor, q_mask: torch.Tensor, n_queries: i
     return n_masks, stride
 
 
+def _mask_table(masks, q_mask: torch.Tensor, n_queries: int, n_rows: int,
+                device: torch.device) -> torch.Tensor:
+    """Argument checks of DenseIndex.topk_mask_ptrs and SparseIndex.topk_mask_ptrs, and the call's
+    pointer table: an int64 device tensor [max(n_masks, 1)] holding each mask's address (0 for
+    None: unfiltered). Every mask is a row_mask of topk (its own int64 device tensor of
+    >= ceil(rows / 64) words); the caller keeps `masks` referenced until the call is enqueued."""
+    if not isinstance(masks, (list, tuple)):
+        raise ValueError("masks must be a list of int64 device tensors (None: unfiltered)")
+    for m in masks:
+        _check_row_mask(m, n_rows)
+        if m is not None and (m.device != device or not m.is_contiguous()):
+            raise ValueError("every mask must be a contiguous tensor on the index's device")
+    if not isinstance(q_mask, torch.Tensor) or q_mask.dtype != torch.int32 or q_mask.dim() != 1 \
+            or not q_mask.is_contiguous():
+        raise ValueError("q_mask must be a contiguous 1-D int32 tensor")
+    if int(q_mask.numel()) != n_queries:
+        raise ValueError(f"q_mask names {q_mask.numel()} masks for {n_queries} queries")
+    if not q_mask.is_cuda and n_queries and not (-1 <= int(q_mask.min()) and
+                                                 int(q_mask.max()) < len(masks)):
+        raise ValueError(f"q_mask entries must be in [-1, {len(masks)})")
+    addrs = [0 if m is None else int(m.data_ptr()) for m in masks] or [0]
+    return torch.tensor(addrs, dtype=torch.int64, device=device)
+
+
 def _on_device(t: torch.Tensor, device: torch.device) -> torch.Tensor:
     return t if t.is_cuda else t.to(device)
 
@@ -287,6 +311,30 @@ class DenseIndex:
         call("armi_dense_topk_qmask", self._handle, ptr(queries), b, k, ptr(row_masks), stride,
              ptr(q_mask), n_masks, ptr(out.scores), ptr(out.ids), ptr(out.rank), ptr(out.count),
              ptr(out.flags), ptr(workspace), workspace.numel(), stream_handle())
+        return out
+
+    def topk_mask_ptrs(self, queries: torch.Tensor, k: int, masks: list, q_mask: torch.Tensor,
+                       workspace: torch.Tensor | None = None, out: TopK | None = None) -> TopK:
+        """topk_masks with every mask a tensor of its own (armi_dense_topk_qmask_ptrs): masks is a
+        list of row_mask tensors (topk's convention; None = unfiltered) that are read in place
+        through a table of their addresses instead of being stacked; q_mask int32 [B] names each
+        query's entry of the list, or -1. The same results, bit for bit, as topk_masks over the
+        stacked masks. The tensors of `masks` must stay alive until the call has run on the
+        device (they are referenced here until it is enqueued; the stream orders the rest)."""
+        _check_fp16_2d(queries, "queries", self.dim)
+        _check_k(k)
+        b = int(queries.shape[0])
+        dev = self.device
+        table = _mask_table(masks, q_mask, b, self.n_rows, dev)
+        q_mask = _on_device(q_mask, dev)
+        if out is None:
+            out = TopK.empty(b, k, dev, rank=True)
+        if b == 0:
+            return out
+        workspace = _workspace(workspace, self.qmask_workspace_bytes(b, k, len(masks)), dev)
+        call("armi_dense_topk_qmask_ptrs", self._handle, ptr(queries), b, k, ptr(table),
+             ptr(q_mask), len(masks), ptr(out.scores), ptr(out.ids), ptr(out.rank),
+             ptr(out.count), ptr(out.flags), ptr(workspace), workspace.numel(), stream_handle())
         return out
 
     def rowlist_workspace_bytes(self, n_queries: int, k: int, max_list_rows: int) -> int:
@@ -495,6 +543,27 @@ class SparseIndex:
              b, k, ptr(row_masks) if n_masks else None, stride, ptr(q_mask), n_masks,
              ptr(out.scores), ptr(out.ids), ptr(out.count), ptr(out.flags), ptr(workspace),
              workspace.numel(), stream_handle())
+        return out
+
+    def topk_mask_ptrs(self, q_indptr: torch.Tensor, q_indices: torch.Tensor,
+                       q_values: torch.Tensor, k: int, masks: list, q_mask: torch.Tensor,
+                       workspace: torch.Tensor | None = None) -> TopK:
+        """topk_masks with every mask a tensor of its own (armi_sparse_topk_qmask_ptrs; the mask
+        arguments as DenseIndex.topk_mask_ptrs): the same results, bit for bit, as topk_masks over
+        the stacked masks."""
+        _check_k(k)
+        b = int(q_indptr.numel()) - 1
+        dev = self.device
+        table = _mask_table(masks, q_mask, max(b, 0), self.n_rows, dev)
+        q_mask = _on_device(q_mask, dev)
+        out = TopK.empty(b, k, dev, rank=False)
+        if b == 0:
+            return out
+        workspace = _workspace(workspace, self.workspace_bytes(b, k), dev)
+        call("armi_sparse_topk_qmask_ptrs", self._handle, ptr(q_indptr), ptr(q_indices),
+             ptr(q_values), b, k, ptr(table), ptr(q_mask), len(masks), ptr(out.scores),
+             ptr(out.ids), ptr(out.count), ptr(out.flags), ptr(workspace), workspace.numel(),
+             stream_handle())
         return out
 
     @staticmethod

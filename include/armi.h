@@ -61,7 +61,9 @@ extern "C" {
  * nothing removed. 5: armi_sparse_tail_topk (+ _workspace_bytes, _chunk_rows); nothing removed.
  * 6: per-query row masks (armi_dense_topk_qmask, + _supported, _workspace_bytes,
  * armi_sparse_topk_qmask, ARMI_FLAG_QMASK); nothing removed. Added since, version unchanged (a
- * caller resolves them by name): armi_dense_tail_topk_qmask, armi_sparse_tail_topk_qmask. */
+ * caller resolves them by name): armi_dense_tail_topk_qmask, armi_sparse_tail_topk_qmask;
+ * armi_dense_topk_qmask_ptrs, armi_sparse_topk_qmask_ptrs (the masks through a pointer table),
+ * armi_stream_create_ex (ARMI_STREAM_QUERY_MASKS), armi_stream_stats_ex, armi_stream_loadgen_ex. */
 #define ARMI_ABI_VERSION 6
 
 /* flags written per query by the top-k entry points */
@@ -289,6 +291,28 @@ int armi_dense_topk_qmask(const armi_index* index, const uint16_t* queries, int 
                           double* out_rank, int32_t* out_count, uint32_t* out_flags,
                           void* workspace, size_t workspace_bytes, hipStream_t stream);
 
+/* armi_dense_topk_qmask with the masks addressed through a table of pointers instead of a stack:
+ * the form a server holds, which receives one caller-owned mask per request and would otherwise
+ * copy n * rows / 8 bytes per batch to stack them.
+ *   mask_ptrs          device array of n_masks device pointers, each naming an 8-byte-aligned
+ *                      bitmask of at least ceil(rows / 64) uint64 words over the index's rows
+ *                      (armi_dense_topk's row_mask convention; bits past the last row are ignored;
+ *                      no word at or past ceil(rows / 64) is read). A null entry = unfiltered.
+ *                      May be null when n_masks = 0.
+ *   q_mask             as armi_dense_topk_qmask: an entry outside [0, n_masks) is treated as -1
+ *                      and never indexes the table.
+ * The result of query q is bit for bit armi_dense_topk_qmask's for the same masks (ids, scores,
+ * rank keys, counts, padding; flags carry ARMI_FLAG_QMASK). Covers the calls
+ * armi_dense_qmask_supported reports 1 for (else ARMI_ERR_UNSUPPORTED); the workspace is
+ * armi_dense_qmask_workspace_bytes. Null pointers, n_masks < 0, k outside [1, 240] and a short
+ * workspace return ARMI_ERR_INVALID before any device work. No host synchronisation;
+ * graph-capture safe (the table and the masks are read when the kernels run). */
+int armi_dense_topk_qmask_ptrs(const armi_index* index, const uint16_t* queries, int n_queries,
+                               int k, const uint64_t* const* mask_ptrs, const int32_t* q_mask,
+                               int n_masks, float* out_scores, int64_t* out_ids, double* out_rank,
+                               int32_t* out_count, uint32_t* out_flags, void* workspace,
+                               size_t workspace_bytes, hipStream_t stream);
+
 size_t armi_dense_exact_workspace_bytes(const armi_index* index, int n_queries, int k);
 /* Exhaustive exact scan with the same outputs and ranking as armi_dense_topk. */
 int armi_dense_exact_topk(const armi_index* index, const uint16_t* queries, int n_queries, int k,
@@ -361,6 +385,26 @@ int armi_stream_create(const armi_index* index, int k, int max_batch, double max
  * dense branch (dense top-k, cosine scores). k <= 120. Both indexes must outlive the server. */
 int armi_stream_create_hybrid(const armi_index* index, const armi_sparse_index* sparse, int k,
                               int rrf_k, int max_batch, double max_wait_us, armi_stream** out);
+/* Both of the above with creation flags (sparse null: a dense server; flags 0: exactly the server
+ * armi_stream_create / armi_stream_create_hybrid make, which are this call with flags 0).
+ * ARMI_STREAM_QUERY_MASKS: one filter per request inside one coalesced batch. A query whose
+ * row_mask differs from the collecting batch's no longer closes it: a batch leaves when it is full
+ * or its first query has waited max_wait_us, whatever its filters. Each slot keeps its queries'
+ * mask pointers (a pinned and a device array of max_batch pointers, max_batch int32 of q_mask)
+ * and copies them to the device next to the queries. A batch whose queries all carry the same
+ * pointer (null included) runs the calls of a server without the flag (armi_dense_topk /
+ * armi_sparse_topk with that mask); a mixed batch takes its dense list from
+ * armi_dense_topk_qmask_ptrs, in consecutive calls of at most 128 queries, and on a hybrid server
+ * its sparse list from one armi_sparse_topk_qmask_ptrs call; fusion, copies and the per-query
+ * branches are unchanged, and every answer is bit for bit the one a server without the flag
+ * gives. The flag needs armi_dense_qmask_supported(index, min(max_batch, 128), kp), kp = k on a
+ * dense server and 2k on a hybrid one: otherwise (kp > 64, or an index without an int8 image)
+ * the call returns ARMI_ERR_UNSUPPORTED, it does not fall back. The caller's promise about a mask
+ * is armi_stream_submit_ex's: alive and unchanged until the ticket's wait has returned. */
+#define ARMI_STREAM_QUERY_MASKS 1u
+int armi_stream_create_ex(const armi_index* index, const armi_sparse_index* sparse, int k,
+                          int rrf_k, int max_batch, double max_wait_us, unsigned flags,
+                          armi_stream** out);
 /* Stops the server (no new batches; blocked submitters and waiters wake and return an error);
  * the server stays allocated until armi_stream_destroy. */
 int armi_stream_stop(armi_stream* server);
@@ -385,7 +429,8 @@ int armi_stream_submit_hybrid(armi_stream* server, const uint16_t* query,
  * bitmask over the store's ordinals (armi_dense_topk's row_mask: the Qdrant payload filter),
  * caller-owned, unchanged and alive until the ticket's wait has returned; it applies to every
  * list of the query (dense, sparse, both prefetches). A batch holds queries of one row_mask: a
- * query with another mask closes the collecting batch (it leaves at once) and opens the next. */
+ * query with another mask closes the collecting batch (it leaves at once) and opens the next,
+ * unless the server was created with ARMI_STREAM_QUERY_MASKS (armi_stream_create_ex). */
 #define ARMI_STREAM_AUTO 0
 #define ARMI_STREAM_DENSE 1
 #define ARMI_STREAM_SPARSE 2
@@ -402,6 +447,10 @@ int armi_stream_submit_ex(armi_stream* server, const uint16_t* query, const int3
 int armi_stream_wait(armi_stream* server, int64_t ticket, float* scores, int64_t* ids,
                      double* rank, int32_t* count, int32_t* mode, double timeout_us);
 int armi_stream_stats(armi_stream* server, int64_t* batches, int64_t* queries);
+/* The same plus mixed_batches: the batches answered through the *_qmask_ptrs calls (always 0 on a
+ * server without ARMI_STREAM_QUERY_MASKS). */
+int armi_stream_stats_ex(armi_stream* server, int64_t* batches, int64_t* queries,
+                         int64_t* mixed_batches);
 /* Native open-loop load generator (bench.py --workload stream): n_queries arrivals as a
  * Poisson process at `qps` from one thread, query i = row (i % n_vectors) of `queries` (host
  * fp16 [n_vectors][dim]) with, when q_indptr is non-null, the sparse terms of CSR row
@@ -414,6 +463,15 @@ int armi_stream_loadgen(armi_stream* server, const uint16_t* queries, const int3
                         int64_t n_queries, double qps, uint64_t seed, double* latency_us,
                         double* elapsed_s, int64_t* completed, int64_t* out_ids,
                         int32_t* out_count);
+/* The same with a payload filter per arrival: masks is a host array of n_masks device pointers
+ * (armi_stream_submit_ex's row_mask; a null entry = unfiltered) and arrival i carries
+ * masks[i % n_masks]; n_masks = 0 is armi_stream_loadgen. The masks stay alive for the call. */
+int armi_stream_loadgen_ex(armi_stream* server, const uint16_t* queries, const int32_t* q_indptr,
+                           const int32_t* q_indices, const float* q_values, int64_t n_vectors,
+                           int64_t n_queries, double qps, uint64_t seed,
+                           const uint64_t* const* masks, int64_t n_masks, double* latency_us,
+                           double* elapsed_s, int64_t* completed, int64_t* out_ids,
+                           int32_t* out_count);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Sparse (lexical-weight) store                                                              */
@@ -481,6 +539,20 @@ int armi_sparse_topk_qmask(const armi_sparse_index* index, const int32_t* q_indp
                            const int32_t* q_mask, int n_masks, float* out_scores,
                            int64_t* out_ids, int32_t* out_count, uint32_t* out_flags,
                            void* workspace, size_t workspace_bytes, hipStream_t stream);
+
+/* armi_sparse_topk_qmask with the masks addressed through a table of pointers (mask_ptrs, q_mask,
+ * n_masks: armi_dense_topk_qmask_ptrs's conventions, over the sparse index's rows). The result of
+ * query q is bit for bit armi_sparse_topk_qmask's for the same masks; out_flags carry
+ * ARMI_FLAG_QMASK. Covers everything armi_sparse_topk covers; the workspace is
+ * armi_sparse_workspace_bytes(index, n_queries, k). A null pointer, n_masks < 0, k outside
+ * [1, 240] and a short workspace return ARMI_ERR_INVALID before any device work. No host
+ * synchronisation; graph-capture safe. */
+int armi_sparse_topk_qmask_ptrs(const armi_sparse_index* index, const int32_t* q_indptr,
+                                const int32_t* q_indices, const float* q_values, int n_queries,
+                                int k, const uint64_t* const* mask_ptrs, const int32_t* q_mask,
+                                int n_masks, float* out_scores, int64_t* out_ids,
+                                int32_t* out_count, uint32_t* out_flags, void* workspace,
+                                size_t workspace_bytes, hipStream_t stream);
 
 /* Sparse dot-product top-k over given rows (armi_dense_rowlist_topk's list encoding: list_ptr,
  * list_rows, q_list, n_lists, max_list_rows), computed from the forward CSR the caller built the
